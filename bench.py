@@ -3,6 +3,15 @@
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|f32|fp8]
                   [--preset vit_b16_224|vit_b16_640|vit_l16_384|c1]
+                  [--dump-outputs DIR] [--full]
+  A plain run sets up, runs W warm-up and K timed steps, writes the last timed step's outputs
+  if --dump-outputs is given and prints the result line.  --full adds what takes runs of its
+  own: the per-kernel / roofline pass (`kernels`, `roofline`, `profiled_ms_per_step`), the
+  gather check (`gather_ok`), the f32 / split-bf16 parity mode (`parity_mode`, headline
+  config only) and the torch-CPU baseline (`cpu_baseline`).
+  --dump-outputs DIR: DIR/logits.npy and DIR/detections.npy (float32; N > 1 also
+  DIR/gathered_detections.npy), what model.detect returned in the last timed step on rank 0.
+  Weights and images come from fixed seeds, so two builds can be compared output for output.
   N > 1 either under a launcher (one rank per GPU, RANK/LOCAL_RANK/WORLD_SIZE from env):
       python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
   or standalone: `python bench.py --gpus N` starts the N rank processes itself (before
@@ -12,9 +21,9 @@
 One step = one forward of B images per rank (images already resident in HBM) + the
 device-side decode (transform_predictions) + the RCCL all-gather of the (B, 17, 6)
 detections over all ranks (the path's only exchange; skipped at N = 1).
-Prints ONE JSON line on rank 0; after the timed region every rank checks that the gathered
-detections hold its own shard bit for bit (`gather_ok`) and reports its own time
-(`rank_ms_min` / `rank_ms_max` over ranks).
+Prints ONE JSON line on rank 0; every rank reports its own time (`rank_ms_min` /
+`rank_ms_max` over ranks), and with --full (or --dry-run) every rank checks after the timed
+region that the gathered detections hold its own shard bit for bit (`gather_ok`).
 """
 import argparse
 import json
@@ -296,6 +305,25 @@ def cpu_baseline(model, kw, shape, preset):
             "cases": cases}
 
 
+FULL_KEYS = ("roofline", "kernels", "profiled_ms_per_step", "gather_ok")   # --full only
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: every tensor of `tensors` as <path>/<name>.npy in float32.  At most
+    DUMP_LIMIT_BYTES in all: an array over its share keeps a fixed sample of its rows (sorted
+    draw without replacement from numpy's default_rng(0), the same rows in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(tensors))
+    for name, t in tensors.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.nbytes > share:
+            keep = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -383,6 +411,8 @@ def dry_run(args, world, rank):
     elapsed = spread["max_s"]
     ranks_ok = out.shape[0] == world * B and all(
         bool((out[r * B:(r + 1) * B] == r).all()) for r in range(world))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"gathered_detections": out})
     gather_ok = check_gather(dets, world, rank, B, "cpu")
     if rank == 0:
         print(json.dumps({
@@ -429,7 +459,16 @@ def main():
     ap.add_argument("--graph", type=int, default=0,
                     help="1: the forward of a step is one HIP-graph replay (captured once after "
                          "warm-up); 0: eager vtd_forward calls")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's logits and detections (rank 0) as "
+                         "DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-kernel / roofline pass, the gather check, the parity "
+                         "mode and the CPU baseline (--no-parity-mode / --no-cpu-baseline drop "
+                         "those two); without it only the headline figure is measured")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     os.environ["VTD_STREAMS"] = str(args.streams)      # read once by libvtd.so
 
     if "WORLD_SIZE" not in os.environ:
@@ -469,9 +508,9 @@ def main():
 
     def eager_step():
         logits, dets = model.detect(images)
-        if world > 1:                        # the path's one exchange: RCCL all-gather
-            all_gather_detections(dets, world * B)
-        return logits
+        # the path's one exchange: RCCL all-gather
+        gathered = all_gather_detections(dets, world * B) if world > 1 else None
+        return logits, dets, gathered
 
     step = eager_step
     for _ in range(args.warmup):
@@ -494,9 +533,8 @@ def main():
 
         def step():
             graph.replay()
-            if world > 1:
-                all_gather_detections(g_dets, world * B)
-            return g_logits
+            gathered = all_gather_detections(g_dets, world * B) if world > 1 else None
+            return g_logits, g_dets, gathered
 
         step()
         torch.cuda.synchronize()
@@ -505,37 +543,45 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:      # before anything else runs on the model
+        names = ("logits", "detections", "gathered_detections")
+        dump_outputs(args.dump_outputs, {n: t for n, t in zip(names, last) if t is not None})
     spread = rank_spread(elapsed, world, dev)
     elapsed = spread["max_s"]
     # correctness evidence of the timed path (outside the timed region): this rank's
     # detections, gathered over all ranks, sit bit for bit at its shard offset, all finite
-    _, dets_chk = model.detect(images)
-    gather_ok = check_gather(dets_chk, world, rank, B, dev)
+    gather_ok = None
+    if args.full:
+        _, dets_chk = model.detect(images)
+        gather_ok = check_gather(dets_chk, world, rank, B, dev)
 
     # ---- per-kernel timing: hipEvents recorded around every launch of vtd_forward on
     # the stream it launches on, over K more steps of the same workload.  Profiling runs
     # vtd_forward on one stream (no micro-batch overlap), so each launch's event pair
     # times that kernel alone: the roofline below is the kernel's own, while `value`
-    # (the timed region above) includes the two-stream overlap.
-    L.check(L.lib.vtd_profile_reset())
-    L.check(L.lib.vtd_profile_enable(1))
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        eager_step()                         # profiling hooks run at launch time: eager
-    torch.cuda.synchronize()
-    prof_elapsed = time.perf_counter() - t1
-    L.check(L.lib.vtd_profile_enable(0))
+    # (the timed region above) includes the two-stream overlap.  --full only: a plain run
+    # leaves the counters at zero and drops the keys built from them (FULL_KEYS below).
     import ctypes
     ms = (ctypes.c_double * L.PROF_CLASSES)()
     nl = (ctypes.c_int64 * L.PROF_CLASSES)()
     fl = (ctypes.c_double * L.PROF_CLASSES)()
-    L.check(L.lib.vtd_profile_read(ms, nl, fl, L.PROF_CLASSES))
+    prof_elapsed = 0.0
+    if args.full:
+        L.check(L.lib.vtd_profile_reset())
+        L.check(L.lib.vtd_profile_enable(1))
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            eager_step()                     # profiling hooks run at launch time: eager
+        torch.cuda.synchronize()
+        prof_elapsed = time.perf_counter() - t1
+        L.check(L.lib.vtd_profile_enable(0))
+        L.check(L.lib.vtd_profile_read(ms, nl, fl, L.PROF_CLASSES))
     classes = ["gemm", "attention", "layernorm", "patches", "other"]
     kernels = {c: {"ms_total": ms[i], "launches": int(nl[i]),
                    "avg_us": 1e3 * ms[i] / max(1, nl[i]),
@@ -615,9 +661,12 @@ def main():
         out["mfma_util_hw"] = round(3 * out["mfma_util_attn_mlp"], 4)
         out["roofline"]["frac_hw"] = (round(3 * out["roofline"]["frac"], 4)
                                       if out["roofline"]["frac"] else None)
-    if world == 1 and headline and not args.no_parity_mode:
+    if not args.full:
+        for k in FULL_KEYS:                  # measured or checked by --full's extra passes
+            del out[k]
+    if args.full and world == 1 and headline and not args.no_parity_mode:
         out["parity_mode"] = parity_mode(args, dev, kw)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model, kw, shape, args.preset)
     if rank == 0:
         print(json.dumps(out), flush=True)

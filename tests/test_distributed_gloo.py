@@ -163,3 +163,24 @@ def test_bench_rejects_gpus_world_mismatch():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4",
                         "--dry-run"], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode != 0 and "disagrees" in r.stderr
+
+
+def test_bench_plain_dry_run_dumps_outputs(tmp_path):
+    """--dump-outputs under --dry-run writes the gathered detections of the last timed step
+    as float32, rank r's rows holding r."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
+                        "--dry-run", "--steps", "2", "--warmup", "1", "--batch", "5",
+                        "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=180, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["steps"] == 2 and out["ms_per_step"] >= 0
+    got = np.load(tmp_path / "dump" / "gathered_detections.npy")
+    assert got.dtype == np.float32 and got.shape == (10, 17, 6)
+    assert (got[:5] == 0).all() and (got[5:] == 1).all()
