@@ -297,7 +297,13 @@ int vtd_fold_layernorm(const float* w32_dev, int N, int K, int ldw, const float*
  * dtype VTD_BF16X3 (the split-bf16 parity mode): qkv is fp32, every product runs as three
  * bf16 MFMA products (hi.hi + lo.hi + hi.lo, fp32 softmax statistics), and out is the
  * split-bf16 A operand of the attention-output Dense, [hi | lo] in two ldo / 2 wide pieces
- * (ldo % 2 == 0, ldo / 2 >= heads*dkp; columns [heads*dkp, ldo / 2) not written). */
+ * (ldo % 2 == 0, ldo / 2 >= heads*dkp; columns [heads*dkp, ldo / 2) not written).
+ * scale must be positive and finite (else VTD_ERR_INVALID_ARG).  Any finite inputs whose
+ * scaled scores scale * log2(e) * q.k (every partial sum over d) are finite in fp32 give a
+ * finite result within the mode's tolerance (2e-5 of max(1, max |O|) for VTD_F32 /
+ * VTD_BF16X3, 2e-2 for VTD_BF16), whatever the size or sign of the scores: no kernel's
+ * running max costs a row more than fp32 rounding of its scores
+ * (tests/test_gpu_attention_patterns.py). */
 int vtd_attention(const void* qkv_dev, int B, int N, int heads, int dkp, int ldqkv,
                   float scale, void* out_dev, int ldo, int dtype, void* stream);
 

@@ -273,8 +273,9 @@ def test_attention_persistent_equals_per_pair_kernel(L, cuda, monkeypatch, B, N,
     128 < N <= 256) against the per-(image, head) kernel, at the C2 shape (3072 pairs, 12 per
     workgroup) and ragged ones.  Its softmax takes the row's true max in one pass (all keys
     are in LDS) where the streaming kernel keeps a deferred running max, so P rounds to bf16
-    differently: equal to within bf16 rounding of P (both are checked against fp64 in
-    test_attention)."""
+    differently: equal to within bf16 rounding of P.  Against fp64: the persistent kernel in
+    test_attention, the per-pair kernel this knob picks at these N (8 waves, knob 2) in
+    test_gpu_attention_patterns.py."""
     dkp = 64
     ld = 3 * H * dkp + 8
     g = torch.Generator().manual_seed(N + H)
@@ -299,8 +300,9 @@ def test_attention_persistent_equals_per_pair_kernel(L, cuda, monkeypatch, B, N,
 def test_attention_long_sequence_equals_streaming_kernel(L, cuda, B, N, H):
     """The long-sequence LDS-DMA kernel (knob 6, opt-in) against the
     register-staged streaming kernel (knob 2) at the C3 / C5 shapes and ragged ones: the same
-    64-key chunks and deferred-rescale online softmax, so equal to within bf16 rounding of P
-    (both against fp64 in test_attention)."""
+    64-key chunks and deferred-rescale online softmax, so equal to within bf16 rounding of P.
+    Against fp64: knob 6 in test_attention, knob 2 in test_gpu_attention_patterns.py; the
+    default at N > 256 (the same 8-wave kernel) in test_attention."""
     dkp = 64
     ld = 3 * H * dkp + 8
     g = torch.Generator().manual_seed(N + H)
@@ -380,6 +382,13 @@ def test_bad_args_raise_value_error(L, cuda):
     with pytest.raises(ValueError):
         L.check(L.lib.vtd_gemm(16, 16, 30, 1, 32, 1, 32, L.BF16, ctypes.byref(e),
                                L.stream_ptr()), "gemm")
+    # attention: the kernels scale the row max, so the scale must be positive and finite
+    x = torch.zeros(64, 3 * 64, dtype=torch.bfloat16, device=cuda)
+    y = torch.zeros(64, 64, dtype=torch.bfloat16, device=cuda)
+    for scale in (-0.125, 0.0, float("inf"), float("nan")):
+        with pytest.raises(ValueError):
+            L.check(L.lib.vtd_attention(x.data_ptr(), 1, 64, 1, 64, 192, scale, y.data_ptr(), 64,
+                                        L.BF16, L.stream_ptr()), "attention")
 
 
 @pytest.mark.parametrize("M,N,K,act,out_dtype", [

@@ -185,6 +185,12 @@ def test_invalid_op_args_raise_before_any_launch(L):
         L.check(L.lib.vtd_gemm(16, 16, 30, 1, 32, 1, 32, L.BF16, ctypes.byref(e), None))
     with pytest.raises(ValueError):
         L.check(L.lib.vtd_attention(None, 1, 4, 1, 48, 144, 1.0, None, 48, L.BF16, None))
+    # attention scale: positive and finite (non-null dummy pointers: rejected before any use)
+    for scale in (-0.125, 0.0, float("inf"), float("nan")):
+        assert L.lib.vtd_attention(1, 1, 4, 1, 64, 192, scale, 1, 64, L.BF16, None) == -1
+        assert b"scale" in L.lib.vtd_last_error()
+        assert L.lib.vtd_attention_mx8(1, 1, 4, 2, 64, 384, scale, 1, 128, 1, 4, None) == -1
+        assert b"scale" in L.lib.vtd_last_error()
     with pytest.raises(ValueError):
         L.check(L.lib.vtd_layernorm(None, L.F32, 1, 4, 4, None, None, 1e-3, None, 4, L.F32, None))
     # split-bf16 A operand (dtype VTD_BF16X3): K = 3 P with P % 64 == 0, lda >= 2 P

@@ -17,6 +17,7 @@
 // k = 2E*step + h*E + j; accumulator register rho holds row (rho&3) + 8(rho>>2) + 4h.
 #include <stdlib.h>
 
+#include <cmath>
 #include <type_traits>
 #include <utility>
 
@@ -325,6 +326,9 @@ __global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void
   constexpr bool OFFM = NWG == 4;
   constexpr bool SUMMFMA = OFFM && DKP <= 64;
   float m_run = OFFM ? 0.f : -INFINITY, l_run = 0.f;
+  // OFFM: what the bf16 m_run leaves of a lane's fp32 max (the max used is m_run + m_res);
+  // non-zero only where |m_run| >= 256, see the rescale below
+  float m_res = 0.f;
   const bf16_t one_bf16 = 0x3F80;
   const bf16x8 a_e0 = {(short)(half == 0 ? one_bf16 : 0), 0, 0, 0, 0, 0, 0, 0};
   const bf16x8 a_ones = {(short)one_bf16, (short)one_bf16, (short)one_bf16, (short)one_bf16,
@@ -424,12 +428,21 @@ __global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void
       // bf16 P operand's range, l and O in fp32); the final 1/l normalises whatever max was
       // used consistently for O and l.  The first chunk always sets the max.
       if constexpr (OFFM) {
-        if (__builtin_amdgcn_ballot_w64(c == 0 || mx > 8.f)) {
-          const float m_new = bf16_round(m_run + (c == 0 ? mx : fmaxf(mx, 0.f)));
+        if (__builtin_amdgcn_ballot_w64(c == 0 || mx > m_res + 8.f)) {
+          // the new max in fp32, and its bf16 rounding (kept finite) for the MFMA column
+          const float m_tgt = m_run + (c == 0 ? mx : fmaxf(mx, m_res));
+          const float bf16_max = __uint_as_float(0x7F7F0000u);
+          const float m_new = fminf(fmaxf(bf16_round(m_tgt), -bf16_max), bf16_max);
+          // from |max| = 256 on one bf16 ulp exceeds 1: the rounding error, up to half an ulp,
+          // would be the exponent of the row's largest P (2^254 at a max of 65790, 0 for every
+          // P at -65790).  There the lane keeps the fp32 residual max - m_run (exact: m_new is
+          // m_tgt rounded) and subtracts it from the scores below; ordinary scores keep 0.
+          const float res_new = fabsf(m_new) >= 256.f ? m_tgt - m_new : 0.f;
           const float dlt = m_new - m_run;
           // (first chunk: O and l are still 0; dlt may be any size there)
-          const float alpha = c == 0 ? 0.f : __builtin_amdgcn_exp2f(-dlt);
+          const float alpha = c == 0 ? 0.f : __builtin_amdgcn_exp2f((m_res - res_new) - dlt);
           m_run = m_new;
+          m_res = res_new;
           b_m[0] = (short)(half == 0 ? f32_to_bf16(-m_new) : 0);
           l_run *= alpha;
           osum[0] *= alpha;
@@ -441,6 +454,13 @@ __global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void
           for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[kb][r] -= dlt;
+        }
+        // wave-uniform, never taken by a wave whose row maxima are all below 256 in magnitude
+        if (__builtin_amdgcn_ballot_w64(m_res != 0.f)) {
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[kb][r] -= m_res;
         }
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
@@ -1741,6 +1761,8 @@ int attention_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqk
   VTD_CHECK_ARG(qkv && out, "attention: null pointer");
   VTD_CHECK_ARG(B > 0 && N > 0 && heads > 0, "attention: bad B/N/heads");
   VTD_CHECK_ARG(dkp == 32 || dkp == 64 || dkp == 128, "attention: dkp must be 32/64/128");
+  // the kernels scale the row max, not every score: only a max for a positive scale
+  VTD_CHECK_ARG(scale > 0 && std::isfinite(scale), "attention: scale must be positive and finite");
   VTD_CHECK_ARG(dtype == VTD_F32 || dtype == VTD_BF16 || dtype == VTD_BF16X3,
                 "attention: bad dtype");
   // VTD_BF16X3: f32 qkv in, the split-bf16 operand [hi | lo] out (ldo = 2 P, P >= inner)
@@ -1811,6 +1833,8 @@ int attention_mx8_launch(const void* qkv, int B, int N, int heads, int dkp, int 
   VTD_CHECK_ARG(qkv && q && s, "attention_mx8: null pointer");
   VTD_CHECK_ARG(B > 0 && N > 0 && heads > 0, "attention_mx8: bad B/N/heads");
   VTD_CHECK_ARG(dkp == 32 || dkp == 64 || dkp == 128, "attention_mx8: dkp must be 32/64/128");
+  VTD_CHECK_ARG(scale > 0 && std::isfinite(scale),
+                "attention_mx8: scale must be positive and finite");
   VTD_CHECK_ARG((heads * dkp) % 128 == 0,
                 "attention_mx8: heads * dkp must be a multiple of 128 (whole MX K-steps)");
   VTD_CHECK_ARG(ldqkv >= 3 * heads * dkp && ldqkv % 8 == 0 && ldq >= heads * dkp && ldq % 16 == 0,
