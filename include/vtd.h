@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define VTD_ABI_VERSION 16
+#define VTD_ABI_VERSION 17
 #define VTD_KALIGN 64          /* K / row padding granule, elements              */
 #define VTD_MAX_MLP 16         /* max encoder_mlp_quantities                     */
 #define VTD_MAX_HEAD 64        /* max mlp_head layers * repeats                   */
@@ -437,6 +437,61 @@ int vtd_map_update(float* latest_positive_bboxes, float* labels_quantity_per_ima
                    const float* y_pred_dev, int batch, int boxes, void* stream);
 int vtd_map_result(const float* latest_positive_bboxes, const float* labels_quantity_per_image,
                    const uint8_t* showed_up_classes, float* out_dev, void* stream);
+
+/* ---------------------------------------------------------------- loss --------- */
+/* (ABI 17) The reference's validation loss, forward value only: no gradients.
+ * ciou_calculator with diagonal_calculator (vtd.py:878-1015), elementwise over n box pairs,
+ * same argument conventions as vtd_iou (the last 4 of `stride` floats are (x, y, height,
+ * width)).  float32 in the reference's operation order:
+ *   iou     = vtd_iou's value
+ *   r_diou  = (rho / (c + 1e-8))^2, rho the centre distance, c the diagonal of the enclosing
+ *             box (max - min of the four edges per axis: what the reference's sort yields)
+ *   v       = (atan(w_l / (h_l + 1e-8)) - atan(w_p / (h_p + 1e-8)))^2 * 4 / pi2, pi2 the
+ *             float32 square of float32(pi) (tf.square(np.pi), vtd.py:992)
+ *   alpha   = v / ((1 - iou) + v + 1e-8)
+ *   out_dev[i] = 1 - iou + r_diou + alpha v, or iou - r_diou when get_diou != 0. */
+int vtd_ciou(const float* label_bbox_dev, const float* pred_bbox_dev, int64_t n, int stride,
+             int get_diou, float* out_dev, void* stream);
+/* diagonal_calculator (vtd.py:878-943) alone: out_dev[i] = c above. */
+int vtd_diagonal(const float* label_bbox_dev, const float* pred_bbox_dev, int64_t n, int stride,
+                 float* out_dev, void* stream);
+
+/* my_custom_loss (vtd.py:1122-1265) of one batch.  y_true_dev / y_pred_dev: fp32
+ * [B][boxes][6] rows (objectness, class, x, y, height, width), any boxes >= 1; labels mark
+ * empty rows [0, -8, -8, -8, -8, -8].
+ *   from_logits = 1: y_pred holds the model's raw logits, decoded inline by vtd_decode's own
+ *     device function (bit-identical to vtd_decode followed by from_logits = 0);
+ *   from_logits = 0: y_pred is decoded already (use_transform_predictions=False).
+ * objectness_mean: over all B * boxes slots, the Keras 2.9 binary cross-entropy
+ *   -(y log(p_c + 1e-7) + (1 - y) log(1 - p_c + 1e-7)), p_c = clip(p, 1e-7, 1 - 1e-7), times
+ *   (1 - p_t)^2 with p_t = y p + (1 - y)(1 - p) of the unclipped p when focal_binary_loss
+ *   (BinaryFocalCrossentropy, gamma 2, no class balancing, no label smoothing).
+ * A slot is positive when isclose(y_true[..., 0], 1) (rtol 1e-5, atol 1e-8).  Over the
+ * positive slots: classification_mean of (coefficient |class error|)^exponent (x * x when
+ * exponent == 2) and ciou_mean of vtd_ciou's loss; both 0 when the batch has no positive
+ * slot.  Only positive slots reach a division or an atan, every slot's clipped objectness
+ * a log: the -8 padding meets none of them.
+ *   total = objectness_mean + classification_mean * weight_classification
+ *           + ciou_mean * weight_ciou
+ * out_dev: fp32 [5] = total, objectness_mean, classification_mean, ciou_mean,
+ * positive_count.  running_dev (nullable): double [2], the kernel adds total * B and B to it
+ * -- the Keras loss metric's batch-size weighted mean is running[0] / running[1].
+ * Per-slot values are float32 in the reference's operation order; the sums run in fp64 in
+ * a fixed order inside one workgroup (no float atomics, no grid-size dependence): the same
+ * inputs give the same bits on every run.  One launch, stream-ordered, no host
+ * synchronisation.  B == 0 writes zeros to out_dev and leaves running_dev alone.
+ * VTD_ERR_INVALID_ARG, before any device call: a NULL p / out_dev / (B > 0) input pointer,
+ * B < 0, boxes <= 0, a non-finite or negative coefficient. */
+typedef struct vtd_loss_params {
+  int focal_binary_loss;        /* 1: BinaryFocalCrossentropy, 0: BinaryCrossentropy  */
+  float coefficient;            /* classification loss (coefficient * error)^exponent  */
+  float exponent;
+  float weight_classification;
+  float weight_ciou;
+  int from_logits;              /* 1: y_pred are logits (use_transform_predictions)   */
+} vtd_loss_params;
+int vtd_loss(const float* y_true_dev, const float* y_pred_dev, int B, int boxes,
+             const vtd_loss_params* p, float* out_dev, double* running_dev, void* stream);
 
 /* Optional per-kernel timing of vtd_forward (hipEvents on `stream`, recorded around
  * every launch while enabled).  vtd_profile_read returns per-class totals in ms

@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must precede loading libvtd.so, see module doc)
 LIB_PATH = os.environ.get("VTD_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                           "libvtd.so")
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 KALIGN = 64
 MAX_MLP = 16
 MAX_HEAD = 64
@@ -81,6 +81,12 @@ class VtdEpilogue(ctypes.Structure):
         ("ldo2", c_int), ("scatter_tokens", c_int), ("lnstat", c_void_p), ("colsum", c_void_p),
         ("statout", c_void_p), ("stat_ld", c_int), ("scale_out", c_void_p),
         ("scale_rows", c_int64), ("detections", c_void_p)]
+
+
+class VtdLossParams(ctypes.Structure):
+    _fields_ = [("focal_binary_loss", c_int), ("coefficient", c_float), ("exponent", c_float),
+                ("weight_classification", c_float), ("weight_ciou", c_float),
+                ("from_logits", c_int)]
 
 
 # name -> (restype, argtypes)
@@ -148,6 +154,10 @@ SIGNATURES = {
     "vtd_map_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                c_void_p]),
     "vtd_map_result": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vtd_ciou": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "vtd_diagonal": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "vtd_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(VtdLossParams),
+                         c_void_p, c_void_p, c_void_p]),
     "vtd_forward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdWeights), c_void_p,
                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vtd_set_knob": (c_int, [c_int, c_int]),

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 
+#include "vtd_box.h"
 #include "vtd_common.h"
 
 #pragma clang fp contract(off)
@@ -28,30 +29,8 @@ namespace {
 constexpr int C = VTD_MAP_CLASSES, L = VTD_MAP_LATEST, P = VTD_MAP_PER_IMAGE;
 constexpr int MAXB = VTD_MAP_MAX_BOXES;
 
-// iou_calculator for one pair of (x, y, h, w) boxes (vtd.py:792-873).  For intersecting
-// boxes the reference's "sort the 4 edges, take 2nd - 3rd" equals min(far) - max(near).
-__device__ __forceinline__ float iou_one(float lx, float ly, float lh, float lw, float px,
-                                         float py, float ph, float pw) {
-  const float ll = lx - lw / 2.f, lr = lx + lw / 2.f;
-  const float pl = px - pw / 2.f, pr = px + pw / 2.f;
-  const float lt = ly - lh / 2.f, lb = ly + lh / 2.f;
-  const float pt = py - ph / 2.f, pb = py + ph / 2.f;
-  const bool cond = (ll < pr) && (lr > pl) && (lt < pb) && (lb > pt);
-  const float ih = cond ? fminf(lb, pb) - fmaxf(lt, pt) : 0.f;
-  const float iw = cond ? fminf(lr, pr) - fmaxf(ll, pl) : 0.f;
-  const float inter = ih * iw;
-  const float pa = pw * ph;
-  const float la = lw * lh;
-  const float uni = (pa + la) - inter;
-  return inter / (uni + 1e-8f);
-}
-
 __device__ __forceinline__ float class_confidence(float c) {   // vtd.py:1367-1376
   return (0.5f - fabsf(c - rintf(c))) / 0.5f;
-}
-
-__device__ __forceinline__ bool isclose(float a, float b) {    // tf.experimental.numpy
-  return fabsf(a - b) <= 1e-8f + 1e-5f * fabsf(b);
 }
 
 __device__ __forceinline__ bool is_positive(const float* row) {  // vtd.py:1458-1463

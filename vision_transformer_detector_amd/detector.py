@@ -156,6 +156,8 @@ class Model:
         self._packed = []              # keeps device buffers alive
         self._ws = None
         self._ws_bytes = 0
+        self.loss = None               # compile(): the loss callable and the metric objects
+        self.metrics = []
         self.set_weights(keras_default_init(self.weight_shapes, seed))
 
     # ---- config helpers
@@ -457,6 +459,85 @@ class Model:
             outs.append(self.forward(x[i:i + batch_size]).cpu().numpy())
         return np.concatenate(outs, axis=0) if outs else np.zeros((0, L.MAX_DETECT, 6),
                                                                   np.float32)
+
+    # ---- compile / evaluate (ipynb:408-435, 835; vtd.py:2172)
+    def compile(self, optimizer=None, loss=None, metrics=None, **_):
+        """keras.Model.compile for the evaluation path: stores `loss` and `metrics`;
+        `optimizer` is ignored (inference only).  `loss` is my_custom_loss or a
+        functools.partial of it (its keywords are read off and evaluate runs the fused
+        from-logits kernel), or any callable (y_true, logits) -> scalar, called per batch.
+        `metrics`: objects with update_state / result / reset_state (MeanAveragePrecision)."""
+        del optimizer
+        if loss is not None and not callable(loss):
+            raise TypeError(f"compile: loss must be callable, got {type(loss).__name__}")
+        metrics = list(metrics or [])
+        for m in metrics:
+            if not all(callable(getattr(m, a, None)) for a in ("update_state", "result",
+                                                               "reset_state")):
+                raise TypeError(f"compile: metric {m!r} needs update_state / result / reset_state")
+        self.loss, self.metrics = loss, metrics
+
+    def _evaluate_batches(self, x, y, batch_size):
+        if y is None:
+            yield from x
+            return
+        if len(x) != len(y):
+            raise ValueError(f"evaluate: {len(x)} images but {len(y)} labels")
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f"evaluate: batch_size must be >= 1, got {batch_size}")
+        for i in range(0, len(x), batch_size):
+            yield x[i:i + batch_size], y[i:i + batch_size]
+
+    def evaluate(self, x, y=None, batch_size=32, verbose=0, return_dict=False, **_):
+        """keras.Model.evaluate: the loss (the Keras loss metric: the mean over batches
+        weighted by batch size) and the compiled metrics over a dataset.  With `y`, `x` and
+        `y` are arrays / tensors split into batches of `batch_size` (the last may be short);
+        with y=None `x` is an iterable of (images, labels) batches.  Per batch the forward,
+        the loss (vtd_loss on the logits, adding into a device accumulator) and every
+        metric's update_state(labels, logits) are queued on the current stream; the one host
+        read comes at the end.  Metrics are reset first, as Keras does.  Returns the loss
+        (no metrics), [loss, *metric results] as Python floats, or with return_dict
+        {"loss": ..., "<metric.name>": ...}."""
+        del verbose
+        if self.loss is None:
+            raise RuntimeError("evaluate: the model has no loss; call "
+                               "compile(loss=my_custom_loss or a functools.partial of it) first")
+        from . import loss as _loss
+        from .metrics import _device_f32
+        params = _loss.fused_loss_params(self.loss)
+        for m in self.metrics:
+            m.reset_state()
+        with torch.cuda.device(self.device):
+            running = torch.zeros(2, dtype=torch.float64, device=self.device)
+            for images, labels in self._evaluate_batches(x, y, batch_size):
+                logits = self.forward(images)
+                labels = _device_f32(labels, self.device)
+                if labels.shape != logits.shape:
+                    raise ValueError(f"evaluate: labels {tuple(labels.shape)} do not match the "
+                                     f"logits {tuple(logits.shape)}")
+                n = logits.shape[0]
+                if n == 0:
+                    continue
+                if params is not None:
+                    _loss._launch(labels, logits, params, running)
+                else:
+                    value = torch.as_tensor(self.loss(labels, logits)).to(
+                        device=self.device, dtype=torch.float64).reshape(())
+                    running[0] += value * n
+                    running[1] += n
+                for m in self.metrics:
+                    m.update_state(labels, logits)
+            # one device-to-host read: the accumulator and every metric's result
+            results = [torch.as_tensor(m.result()).to(device=self.device, dtype=torch.float64)
+                       .reshape(1) for m in self.metrics]
+            read = torch.cat([running, *results]).cpu().tolist()
+        # sum(loss_b * n_b) / sum(n_b); 0 / 0 (no data) is nan, as an empty Keras mean would be
+        values = [read[0] / read[1] if read[1] else float("nan")] + read[2:]
+        if return_dict:
+            names = ["loss"] + [getattr(m, "name", type(m).__name__) for m in self.metrics]
+            return dict(zip(names, values))
+        return values if self.metrics else values[0]
 
     def count_params(self) -> int:
         return int(sum(int(np.prod(s)) for s in self.weight_shapes.values()))
