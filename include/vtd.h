@@ -439,7 +439,8 @@ int vtd_map_result(const float* latest_positive_bboxes, const float* labels_quan
                    const uint8_t* showed_up_classes, float* out_dev, void* stream);
 
 /* ---------------------------------------------------------------- loss --------- */
-/* (ABI 17) The reference's validation loss, forward value only: no gradients.
+/* (ABI 17) The reference's validation loss: the forward values here, the gradients w.r.t.
+ * the prediction below (vtd_loss_grad, vtd_ciou_grad, vtd_decode_grad).
  * ciou_calculator with diagonal_calculator (vtd.py:878-1015), elementwise over n box pairs,
  * same argument conventions as vtd_iou (the last 4 of `stride` floats are (x, y, height,
  * width)).  float32 in the reference's operation order:
@@ -492,6 +493,48 @@ typedef struct vtd_loss_params {
 } vtd_loss_params;
 int vtd_loss(const float* y_true_dev, const float* y_pred_dev, int B, int boxes,
              const vtd_loss_params* p, float* out_dev, double* running_dev, void* stream);
+
+/* Gradients of the loss (additions to ABI 17; nothing above changes).  Analytic float32
+ * derivatives of the graph the reference builds, w.r.t. the prediction; labels are
+ * constants.  The derivatives, DESIGN.md "Loss gradients":
+ *   objectness: d/dp of the cross-entropy on p_c = clip(p, 1e-7, 1 - 1e-7) -- the clip passes
+ *     gradient on its closed interval, 0 outside -- and of the focal factor (1 - p_t)^2
+ *     through the unclipped p; times 1 / (B * boxes);
+ *   class, positive slots only: exponent coefficient (coefficient |d|)^(exponent - 1) sign(d),
+ *     sign(0) = 0; times weight_classification / positives;
+ *   CIoU, positive slots only: through iou, r_diou, v and alpha (no stop_gradient); the
+ *     reference's edge sorts route gradient to whichever edge lands at a position (ties as a
+ *     stable sort); the intersection only under the intersect condition; times weight_ciou /
+ *     positives;
+ *   from_logits = 1: times scale_f s (1 - s) of the decode, s vtd_decode's own sigmoid;
+ *     from_logits = 0: the gradient is w.r.t. the decoded prediction.
+ * Two deliberate deviations from autodiff of the reference: r_diou is differentiated as
+ * (dx^2 + dy^2) / (c + 1e-8)^2 (the same value; the reference's sqrt gives 0/0 at coincident
+ * centres, this form 0 in x and y), and at a kink (tied edges, zero class error, boxes that
+ * just touch) one of the one-sided derivatives is returned.  Every result is finite for
+ * finite inputs with positive box sizes, and bit-identical from run to run.
+ *
+ * vtd_loss_grad: vtd_loss's out_dev[5], bit for bit, and grad_dev fp32 [B][boxes][6] =
+ * d total / d y_pred in ONE launch (one workgroup: vtd_loss's loop also writes each slot's
+ * unscaled derivatives, the positive count goes through LDS, then every thread rescales the
+ * slots it wrote itself; one writer per element, no atomics).  upstream_dev (nullable): one device float that multiplies the gradient, so a
+ * chained backward needs no host read.  Non-positive slots get exactly 0 in channels 1..5.
+ * Arguments as vtd_loss, plus: exponent must be finite and >= 1 (below 1 the class
+ * derivative is unbounded at a zero class error).  B == 0 zeroes out_dev and launches
+ * nothing else. */
+int vtd_loss_grad(const float* y_true_dev, const float* y_pred_dev, int B, int boxes,
+                  const vtd_loss_params* p, const float* upstream_dev, float* out_dev,
+                  float* grad_dev, void* stream);
+/* d vtd_ciou / d pred_bbox (the CIoU loss, or the DIoU with get_diou), elementwise:
+ * grad_dev fp32 [n][stride], the leading stride - 4 channels 0, the last four times
+ * upstream_dev[i] (fp32 [n], nullable = 1).  Arguments as vtd_ciou; n == 0 is a no-op. */
+int vtd_ciou_grad(const float* label_bbox_dev, const float* pred_bbox_dev, int64_t n,
+                  int stride, int get_diou, const float* upstream_dev, float* grad_dev,
+                  void* stream);
+/* d vtd_decode: grad_dev[i] = upstream_dev[i] * scale_f s (1 - s), fp32 [n][6] each (the
+ * [0, 1] clip never closes on a sigmoid).  n == 0 is a no-op. */
+int vtd_decode_grad(const float* logits_dev, const float* upstream_dev, int64_t n,
+                    float* grad_dev, void* stream);
 
 /* Optional per-kernel timing of vtd_forward (hipEvents on `stream`, recorded around
  * every launch while enabled).  vtd_profile_read returns per-class totals in ms

@@ -1,6 +1,9 @@
 """Cost of the validation loss on the device (DESIGN.md "Validation loss"):
  1. us per vtd_loss launch at (256, 17) with from_logits=1, device events around 200
-    launches after a warm-up; beside it vtd_decode + vtd_loss with from_logits=0;
+    launches after a warm-up; beside it vtd_decode + vtd_loss with from_logits=0, one
+    vtd_loss_grad launch (the value and d loss / d logits), and forward + backward of the
+    same loss written in torch operations on the device (what a user would write without
+    the gradient kernel), all measured the same way;
  2. wall time of Model.evaluate over 4 batches of 256 at ViT-B/16 @224 in bf16 against four
     bare forward calls + four MeanAveragePrecision.update_state calls and one result read,
     alternating the two, several rounds.
@@ -33,6 +36,43 @@ def labels_and_logits(rng, batch, boxes=17):
     return y, rng.normal(0, 2, (batch, boxes, 6)).astype(np.float32)
 
 
+def torch_ops_loss(y, logits, coefficient=4.0, exponent=2.0, weight_classification=0.0074,
+                   weight_ciou=10.0):
+    """my_custom_loss in torch operations on the device, masks instead of boolean indexing
+    so that nothing synchronises; r_diou without the sqrt of the centre distance."""
+    eps, keps = 1e-8, 1e-7
+    scale = torch.tensor([1.0, 79.0, 608.0, 608.0, 608.0, 608.0], device=logits.device)
+    d = torch.sigmoid(logits) * scale
+    t, p = y[..., 0], d[..., 0]
+    pc = torch.clamp(p, keps, 1 - keps)
+    bce = -(t * torch.log(pc + keps) + (1 - t) * torch.log(1 - pc + keps))
+    bce = torch.pow(1 - (t * p + (1 - t) * (1 - p)), 2) * bce
+    pos = torch.isclose(t, torch.ones_like(t))
+    count = pos.sum().clamp(min=1)
+    cls = torch.pow(coefficient * torch.abs(d[..., 1] - y[..., 1]), exponent)
+    lb = torch.where(pos[..., None], y[..., 2:], torch.ones_like(y[..., 2:]))
+    pb = torch.where(pos[..., None], d[..., 2:], torch.ones_like(d[..., 2:]))
+    hor = torch.stack([lb[..., 1] - lb[..., 2] / 2, lb[..., 1] + lb[..., 2] / 2,
+                       pb[..., 1] - pb[..., 2] / 2, pb[..., 1] + pb[..., 2] / 2], -1)
+    ver = torch.stack([lb[..., 0] - lb[..., 3] / 2, lb[..., 0] + lb[..., 3] / 2,
+                       pb[..., 0] - pb[..., 3] / 2, pb[..., 0] + pb[..., 3] / 2], -1)
+    cond = ((ver[..., 0] < ver[..., 3]) & (ver[..., 1] > ver[..., 2]) &
+            (hor[..., 0] < hor[..., 3]) & (hor[..., 1] > hor[..., 2]))[..., None]
+    hs = torch.sort(torch.where(cond, hor, torch.zeros_like(hor)), -1).values
+    vs = torch.sort(torch.where(cond, ver, torch.zeros_like(ver)), -1).values
+    inter = (hs[..., 2] - hs[..., 1]) * (vs[..., 2] - vs[..., 1])
+    iou = inter / (pb[..., 3] * pb[..., 2] + lb[..., 3] * lb[..., 2] - inter + eps)
+    ho, vo = torch.sort(hor, -1).values, torch.sort(ver, -1).values
+    eh, ew = ho[..., 3] - ho[..., 0], vo[..., 3] - vo[..., 0]
+    dx, dy = lb[..., 0] - pb[..., 0], lb[..., 1] - pb[..., 1]
+    r_diou = (dx * dx + dy * dy) / torch.square(torch.sqrt(eh * eh + ew * ew) + eps)
+    v = torch.square(torch.atan(lb[..., 3] / (lb[..., 2] + eps)) -
+                     torch.atan(pb[..., 3] / (pb[..., 2] + eps))) * 4 / 9.869605
+    ciou = 1 - iou + r_diou + v / ((1 - iou) + v + eps) * v
+    return (bce.mean() + (cls * pos).sum() / count * weight_classification +
+            (ciou * pos).sum() / count * weight_ciou)
+
+
 def events_us(fn, launches, warmup):
     for _ in range(warmup):
         fn()
@@ -53,6 +93,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=31)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--batches", type=int, default=4)
+    ap.add_argument("--loss-only", action="store_true", help="skip the Model.evaluate part")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("loss_bench needs a HIP device")
@@ -69,6 +110,20 @@ def main():
     out["decode_plus_loss_us"] = events_us(
         lambda: VL._launch(yt, vtd.transform_predictions(lg), plain, running),
         a.launches, a.warmup)
+    out["loss_grad_us"] = events_us(lambda: VL._launch_grad(yt, lg, fused), a.launches, a.warmup)
+    leaf = lg.clone().requires_grad_()
+
+    def torch_ops():
+        leaf.grad = None
+        torch_ops_loss(yt, leaf).backward()
+
+    out["torch_ops_forward_backward_us"] = events_us(torch_ops, a.launches, a.warmup)
+    ours, theirs = VL._launch_grad(yt, lg, fused), (torch_ops_loss(yt, leaf), leaf.grad)
+    out["torch_ops_agreement"] = [abs(ours[0][0].item() - theirs[0].item()),
+                                  (ours[1] - theirs[1]).abs().max().item()]
+    if a.loss_only:
+        print(json.dumps(out))
+        return
 
     model = vtd.create_vision_transformer_detector(**vtd.presets.VIT_B16_224, dtype="bfloat16",
                                                    device=dev)

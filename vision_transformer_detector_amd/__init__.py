@@ -38,13 +38,13 @@ from .detector import (Constants, Model, create_vision_transformer_detector,  # 
                        keras_weight_names, transform_predictions)
 from .metrics import MeanAveragePrecision, iou_calculator  # noqa: F401
 from .loss import (ciou_calculator, diagonal_calculator, get_label_arrays,  # noqa: F401
-                   loss_components, my_custom_loss)
+                   loss_and_grad, loss_components, my_custom_loss)
 from . import presets  # noqa: F401
 from .preprocess import get_image_tensors  # noqa: F401
 
 __all__ = ["Constants", "Model", "create_vision_transformer_detector",
            "transform_predictions", "decode_detections", "detection_list", "presets",
            "MeanAveragePrecision", "iou_calculator", "get_image_tensors",
-           "my_custom_loss", "loss_components", "ciou_calculator", "diagonal_calculator",
-           "get_label_arrays",
+           "my_custom_loss", "loss_components", "loss_and_grad", "ciou_calculator",
+           "diagonal_calculator", "get_label_arrays",
            "enable_device_kernel_arguments"]

@@ -158,6 +158,11 @@ SIGNATURES = {
     "vtd_diagonal": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "vtd_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(VtdLossParams),
                          c_void_p, c_void_p, c_void_p]),
+    "vtd_loss_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(VtdLossParams),
+                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vtd_ciou_grad": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
+                              c_void_p]),
+    "vtd_decode_grad": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "vtd_forward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdWeights), c_void_p,
                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vtd_set_knob": (c_int, [c_int, c_int]),

@@ -539,6 +539,19 @@ class Model:
             return dict(zip(names, values))
         return values if self.metrics else values[0]
 
+    def loss_and_grad(self, images, y_true):
+        """The forward and the compiled loss with its gradient at the logits: (out5,
+        d loss / d logits), both on the device, as loss.loss_and_grad(y_true, model(images),
+        <the compiled keywords>) returns them -- where a backward pass through the model
+        would start.  Needs compile(loss=my_custom_loss or a functools.partial of it)."""
+        from . import loss as _loss
+        params = _loss.fused_loss_params(self.loss) if self.loss is not None else None
+        if params is None:
+            raise ValueError("loss_and_grad: compile(loss=my_custom_loss or a functools.partial "
+                             "of it with keyword arguments) first")
+        with torch.cuda.device(self.device):
+            return _loss.loss_and_grad(y_true, self.forward(images), params=params)
+
     def count_params(self) -> int:
         return int(sum(int(np.prod(s)) for s in self.weight_shapes.values()))
 
@@ -616,14 +629,41 @@ def _to_device(inputs, what):
     return t.to(torch.float32).contiguous(), back
 
 
+class _Decode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src):
+        src = src.detach()
+        out = torch.empty_like(src)
+        if src.numel():
+            with torch.cuda.device(src.device):
+                L.check(L.lib.vtd_decode(src.data_ptr(), src.numel() // 6, out.data_ptr(),
+                                         L.stream_ptr()), "vtd_decode")
+        ctx.save_for_backward(src)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        src, = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        grad = torch.empty_like(src)
+        with torch.cuda.device(src.device):
+            L.check(L.lib.vtd_decode_grad(src.data_ptr(), g.data_ptr(), src.numel() // 6,
+                                          grad.data_ptr(), L.stream_ptr()), "vtd_decode_grad")
+        return grad
+
+
 def transform_predictions(inputs):
     """vtd.py:586-647 on a (…, 6) tensor/array: sigmoid; clip the last 4 to [0, 1];
     [objectness, class * (CLASSES - 1), cx * W, cy * H, h * H, w * W] with (H, W) the
     constant MODEL_IMAGE_SIZE = (608, 608).  Decodes on the GPU (vtd_decode).  The
     reference's callers pass whatever `predict` returned (vtd.py:1164, 1341, 2447), so
     numpy / CPU inputs are staged to the device and the result comes back in the same
-    type (numpy in, numpy out)."""
+    type (numpy in, numpy out).  A tensor that requires grad gets a differentiable result
+    (vtd_decode_grad: scale * s (1 - s) of the decode's own sigmoid)."""
     src, back = _to_device(inputs, "transform_predictions")
+    if src.requires_grad and torch.is_grad_enabled():
+        return back(_Decode.apply(src))
     out = torch.empty_like(src)
     n = src.numel() // 6
     if n:

@@ -4,8 +4,14 @@
 `diagonal_calculator` (vtd.py:878-1015) with the reference's names, arguments and defaults;
 the work runs in libvtd.so (vtd_loss / vtd_ciou / vtd_diagonal, include/vtd.h): one launch
 per batch, fp32 per-slot arithmetic in the reference's order, fp64 fixed-order sums.
-Forward values only -- no gradients, training is out of scope.  `get_label_arrays` (host
-only) builds the reference's label rows (vision_transformer_utilities.py:268-382, 452-507).
+`my_custom_loss`, `loss_components` (its total), `ciou_calculator` and
+`transform_predictions` are differentiable w.r.t. the prediction: when the float32
+prediction tensor requires grad (and grad mode is on) they run as torch.autograd.Functions
+over the analytic gradient kernels (vtd_loss_grad / vtd_ciou_grad / vtd_decode_grad, first
+derivatives only); otherwise they take the value-only path unchanged.  Labels are constants.
+`loss_and_grad` returns the values and d loss / d prediction without autograd.  Backward
+through the model, optimizers and `fit` are out of scope.  `get_label_arrays` (host only)
+builds the reference's label rows (vision_transformer_utilities.py:268-382, 452-507).
 """
 from __future__ import annotations
 
@@ -15,6 +21,7 @@ import math
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 from .metrics import _device_f32
@@ -34,8 +41,11 @@ def ciou_calculator(label_bbox, prediction_bbox, get_diou=None):
     """vtd.py:946-1015: the CIoU loss 1 - IoU + r_diou + alpha * v of the boxes at matching
     positions, or the DIoU (IoU - r_diou) with `get_diou`.  Inputs as `iou_calculator`: the
     same shape (..., k), k >= 4, the last 4 channels (x, y, height, width).  Returns a (...)
-    float32 tensor on the device."""
+    float32 tensor on the device, differentiable w.r.t. `prediction_bbox` (vtd_ciou_grad;
+    the channels before the last four get a zero gradient)."""
     dev, lb, pb, out = _pair(label_bbox, prediction_bbox, "ciou_calculator")
+    if _wants_grad(lb, pb, "ciou_calculator"):
+        return _Ciou.apply(pb, lb, bool(get_diou))
     with torch.cuda.device(dev):
         L.check(L.lib.vtd_ciou(lb.data_ptr(), pb.data_ptr(), out.numel(), lb.shape[-1],
                                1 if get_diou else 0, out.data_ptr(), L.stream_ptr()), "vtd_ciou")
@@ -75,6 +85,71 @@ def _launch(yt, yp, params, running=None):
     return out
 
 
+def _wants_grad(label, pred, what):
+    """The dispatch rule of every differentiable entry point: the gradient path when the
+    float32 prediction tensor requires grad and grad mode is on, else the value-only one."""
+    if not torch.is_grad_enabled():
+        return False
+    if label.requires_grad:
+        raise ValueError(f"{what}: labels are constants; the label tensor requires grad")
+    return pred.requires_grad
+
+
+def _launch_grad(yt, yp, params, upstream=None):
+    """vtd_loss_grad on the current stream of yt's device: (out5, d total / d yp)."""
+    out = torch.empty(5, device=yt.device, dtype=torch.float32)
+    grad = torch.empty_like(yp)
+    with torch.cuda.device(yt.device):
+        L.check(L.lib.vtd_loss_grad(yt.data_ptr(), yp.data_ptr(), yt.shape[0], yt.shape[1],
+                                    ctypes.byref(params), L.ptr(upstream), out.data_ptr(),
+                                    grad.data_ptr(), L.stream_ptr()), "vtd_loss_grad")
+    return out, grad
+
+
+class _Loss(torch.autograd.Function):
+    """(total, the four reported values) with d total / d y_pred computed in the forward's
+    own launch; backward is one multiply and never synchronises."""
+
+    @staticmethod
+    def forward(ctx, yp, yt, params):
+        out, grad = _launch_grad(yt, yp.detach(), params)
+        ctx.save_for_backward(grad)
+        total, parts = out[0], out[1:]
+        ctx.mark_non_differentiable(parts)
+        return total, parts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_total, _g_parts):
+        grad, = ctx.saved_tensors
+        return grad * g_total, None, None
+
+
+class _Ciou(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pb, lb, get_diou):
+        pb = pb.detach()
+        out = torch.empty(lb.shape[:-1], device=lb.device, dtype=torch.float32)
+        with torch.cuda.device(lb.device):
+            L.check(L.lib.vtd_ciou(lb.data_ptr(), pb.data_ptr(), out.numel(), lb.shape[-1],
+                                   1 if get_diou else 0, out.data_ptr(), L.stream_ptr()), "vtd_ciou")
+        ctx.save_for_backward(lb, pb)
+        ctx.get_diou = get_diou
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        lb, pb = ctx.saved_tensors
+        g = g.to(torch.float32).contiguous()
+        grad = torch.empty_like(pb)
+        with torch.cuda.device(lb.device):
+            L.check(L.lib.vtd_ciou_grad(lb.data_ptr(), pb.data_ptr(), g.numel(), lb.shape[-1],
+                                        1 if ctx.get_diou else 0, g.data_ptr(), grad.data_ptr(),
+                                        L.stream_ptr()), "vtd_ciou_grad")
+        return grad, None, None
+
+
 def _batch(y_true, y_pred, what):
     dev = y_pred.device if torch.is_tensor(y_pred) and y_pred.is_cuda else torch.device("cuda")
     yt, yp = _device_f32(y_true, dev), _device_f32(y_pred, dev)
@@ -88,8 +163,14 @@ def loss_components(y_true, y_pred, focal_binary_loss=True, coefficient=4, expon
                     weight_classification=0.0074, weight_ciou=10,
                     use_transform_predictions=True):
     """my_custom_loss with its parts: a float32 [5] device tensor (total, objectness mean,
-    classification mean, CIoU mean, number of positive slots).  No synchronisation."""
+    classification mean, CIoU mean, number of positive slots).  No synchronisation.  Element
+    0 is differentiable w.r.t. y_pred; the other four are reported values."""
     yt, yp = _batch(y_true, y_pred, "loss_components")
+    if _wants_grad(yt, yp, "loss_components"):
+        total, parts = _Loss.apply(yp, yt, loss_params(
+            focal_binary_loss, coefficient, exponent, weight_classification, weight_ciou,
+            use_transform_predictions))
+        return torch.cat([total.reshape(1), parts])
     return _launch(yt, yp, loss_params(focal_binary_loss, coefficient, exponent,
                                        weight_classification, weight_ciou,
                                        use_transform_predictions))
@@ -105,11 +186,38 @@ def my_custom_loss(y_true, y_pred, focal_binary_loss=True,
     float32 device tensor without synchronising: focal (or plain) binary cross-entropy of the
     objectness over every slot + weight_classification * mean (coefficient * |class
     error|)^exponent + weight_ciou * mean CIoU loss, the two means over the positive slots
-    (0 when there are none)."""
+    (0 when there are none).  Differentiable w.r.t. y_pred (first derivatives): when it
+    requires grad the same launch also computes d loss / d y_pred (vtd_loss_grad) and
+    backward multiplies it by the incoming gradient; exponent must then be >= 1."""
     yt, yp = _batch(y_true, y_pred, "my_custom_loss")
+    if _wants_grad(yt, yp, "my_custom_loss"):
+        return _Loss.apply(yp, yt, loss_params(
+            focal_binary_loss, coefficient, exponent, weight_classification, weight_ciou,
+            use_transform_predictions))[0]
     return _launch(yt, yp, loss_params(focal_binary_loss, coefficient, exponent,
                                        weight_classification, weight_ciou,
                                        use_transform_predictions))[0]
+
+
+def loss_and_grad(y_true, y_pred, upstream=None, **kwargs):
+    """(out5, grad) without autograd: loss_components' float32 [5] tensor -- the same bits --
+    and d total / d y_pred, float32 of y_pred's shape (w.r.t. the logits, or the decoded
+    predictions with use_transform_predictions=False), from one launch with no
+    synchronisation.  `upstream`: an optional one-element float32 device tensor that
+    multiplies the gradient on the device.  **kwargs: my_custom_loss's keywords, or
+    params=<vtd_loss_params>."""
+    yt, yp = _batch(y_true, y_pred, "loss_and_grad")
+    params = kwargs.pop("params", None)
+    if params is None:
+        params = loss_params(**kwargs)
+    elif kwargs:
+        raise TypeError("loss_and_grad: params excludes the other keywords")
+    if upstream is not None:
+        upstream = _device_f32(upstream, yt.device)
+        if upstream.numel() != 1:
+            raise ValueError("loss_and_grad: upstream must hold one element")
+    with torch.no_grad():
+        return _launch_grad(yt, yp, params, upstream)
 
 
 def fused_loss_params(loss):
