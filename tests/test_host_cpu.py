@@ -166,6 +166,48 @@ def test_workspace_grows_with_batch(L):
     assert sizes[2] < 64 * sizes[0] * 1.01
 
 
+WORKSPACE_GOLDEN = os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")
+
+
+def workspace_table(L):
+    """vtd_workspace_bytes of the loaded library for CONFIGS x dtype x batch, keyed
+    "C<n>/<dtype>/<batch>": the byte count, or {"error": code} where the library rejects
+    the configuration."""
+    table = {}
+    for ci, kw in enumerate(CONFIGS):
+        for dname in ("F32", "BF16", "FP8", "BF16X3"):
+            for b in (1, 8, 62, 63, 64, 129, 256):
+                n = ctypes.c_size_t()
+                rc = L.lib.vtd_workspace_bytes(
+                    ctypes.byref(_cfg(L, kw, batch=b, dtype=getattr(L, dname))), ctypes.byref(n))
+                table[f"C{ci + 1}/{dname}/{b}"] = n.value if rc == 0 else {"error": rc}
+    return table
+
+
+def test_workspace_bytes_match_recorded_table(L):
+    """The workspace plan is pinned: vtd_workspace_bytes equals, entry by entry, the table in
+    tests/golden/workspace_bytes.json for the four CONFIGS x {F32, BF16, FP8, BF16X3} x batch
+    {1, 8, 62, 63, 64, 129, 256}.  For C2, 62 x 196 rows is just under the two-part threshold
+    of 2 x 24 x 256 rows and 63 just over, so both sides of the micro-batch split decision and
+    the padded-part sizes are covered.
+
+    The table was recorded from a build of the commit BEFORE the runtime was restructured
+    into Part / Plan / Mode / Switches (so it checks that restructuring, and every later
+    change, against the earlier plan, never against the code under test):
+        tools/build_prev.sh <that commit>
+        VTD_LIB_PATH=vision_transformer_detector_amd/libvtd_prev.so python -c "import json; \
+            from tests import test_host_cpu as t; from vision_transformer_detector_amd import _lib; \
+            json.dump(t.workspace_table(_lib), open(t.WORKSPACE_GOLDEN, 'w'), indent=0)"
+    with none of the VTD_* environment switches set.  A change that alters the workspace on
+    purpose re-records the table from its own build and says so."""
+    import json
+    want = json.load(open(WORKSPACE_GOLDEN))
+    got = workspace_table(L)
+    assert sorted(got) == sorted(want) and len(want) == 4 * 4 * 7
+    wrong = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    assert not wrong, wrong
+
+
 @pytest.mark.parametrize("field,value", [("batch", 0), ("patch_size", 0), ("key_dim", 200),
                                          ("mlp_quantities", 17), ("dtype", 7),
                                          ("head_layers", 0)])

@@ -1,5 +1,6 @@
 """Per-dispatch timeline of one vtd_forward from a rocprofv3 --kernel-trace CSV: the last
-complete forward (patches kernel .. decode kernel), each dispatch with its duration, grid
+complete forward (first patches kernel .. last vtd kernel before the next forward: the decode is
+fused into the last GEMM's epilogue), each dispatch with its duration, grid
 and the idle gap before it, plus per-role totals.  Usage: python tools/trace_forward.py CSV [k]
 (k = which forward from the end, default 1)."""
 import csv
@@ -15,10 +16,12 @@ def short(name):
 def main(path, k=1):
     rows = [r for r in csv.DictReader(open(path)) if r["Kind"] == "KERNEL_DISPATCH"]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    starts = [i for i, r in enumerate(rows) if "patches" in r["Kernel_Name"]]
-    ends = [i for i, r in enumerate(rows) if "decode_kernel" in r["Kernel_Name"]]
+    pat = [i for i, r in enumerate(rows) if "patches" in r["Kernel_Name"]]
+    # one start per forward: the patches kernels of its micro-batch parts lie within a stage or two
+    starts = [i for j, i in enumerate(pat) if j == 0 or i - pat[j - 1] > 12]
     s = starts[-k]
-    e = min(i for i in ends if i > s)
+    nxt = min([i for i in starts if i > s], default=len(rows))
+    e = max(i for i in range(s, nxt) if "vtd::" in rows[i]["Kernel_Name"])
     fw = rows[s:e + 1]
     t0 = int(fw[0]["Start_Timestamp"])
     prev_end = t0

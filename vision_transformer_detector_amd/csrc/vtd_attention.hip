@@ -21,7 +21,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "vtd_common.h"
+#include "vtd_launch.h"
 
 namespace vtd {
 

@@ -9,6 +9,12 @@
 
 #include "../../include/vtd.h"
 
+// 1 in the timing-diagnostic build only (`make diag`: extra kernels and environment switches
+// that give WRONG outputs); the product library compiles none of them
+#ifndef VTD_DIAG
+#define VTD_DIAG 0
+#endif
+
 namespace vtd {
 
 // ----------------------------------------------------------------- errors (host)

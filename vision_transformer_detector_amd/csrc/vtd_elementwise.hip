@@ -1,7 +1,7 @@
 // HBM-bound kernels of the forward path: LayerNorm (vtd.py:353-357, 375-379),
 // ExtractImagePatches + flatten (vtd.py:177-206, 279-280), transform_predictions
 // (vtd.py:586-647), and the one-time weight packing.
-#include "vtd_common.h"
+#include "vtd_launch.h"
 
 namespace vtd {
 

@@ -19,6 +19,7 @@
 
 #include "vtd_common.h"
 #include "vtd_gemm_epi.h"
+#include "vtd_launch.h"
 
 namespace vtd {
 
@@ -1594,19 +1595,11 @@ __global__ __launch_bounds__(BNT) void gemm_mx8_pp_kernel(
 }
 }  // namespace
 
-#ifndef VTD_DIAG
-#define VTD_DIAG 0
-#endif
 #if VTD_DIAG
 // Diagnostic build only (`make diag`, vtd_gemm_w4.hip): the one-wave-per-SIMD w4 (bf16) and
 // x4 (MX-fp8) kernels, measured slower than / equal to the ping-pong kernels in the forward
 // (profiles/r03_fwd_ab.log, r03_bench_c5_b128_fp8_mx3_s2.log) and therefore not in the product
 // library.  VTD_GEMM_VARIANT = 12 selects w4; VTD_MX_VARIANT = 2 selects x4, 3 x4 for K >= 2048.
-bool gemm_w4_launch(int M, int N, int K, const bf16_t* A, int lda, const bf16_t* Bt, int ldb,
-                    const vtd_epilogue* epi, int ngw, hipStream_t stream);
-void gemm_mx8_x4_launch(int M, int N, int K, const uint8_t* A, int lda, const uint8_t* sA,
-                        int64_t sa_rows, const uint8_t* Bt, int ldb, const uint8_t* sB,
-                        int64_t sb_rows, const vtd_epilogue* epi, int ngw, hipStream_t stream);
 int mx_variant() {
   const char* v = getenv("VTD_MX_VARIANT");
   return v ? atoi(v) : 1;
@@ -1713,9 +1706,6 @@ bool gemm_mx8_emits_fp8(int M, int N, const vtd_epilogue* e) {
          e->scale_out && e->scale_rows >= M && e->scale_rows % 4 == 0;
 }
 
-int ln_stats_finalize_launch(const float* part, int64_t rows, int slots, int D, float eps,
-                             float* stat, hipStream_t st);
-
 // multi-tile pp2 dynamic LDS: stage 0, then stage 1 overlapped by the epilogue staging and
 // the statistics table (stage 0 takes the next tile's first K-stage during an epilogue)
 constexpr size_t kPP2LdsMax = BSTAGE + 8 * 32 * 68 * 4 + 8 * 128 * 8;
@@ -1792,10 +1782,6 @@ __global__ __launch_bounds__(256) void gemm_splitk_epilogue_kernel(
   epi_store4(e, M, N, m, n, v);
 }
 
-int gemm_launch_ln(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
-                   int dtype, const vtd_epilogue* epi, hipStream_t stream, double flops,
-                   const float* lnpart, int lnslots, int lnD, float lneps);
-
 // the f32 256-tile kernel: the f32-output codes the fp32 mode's forward uses (bias,
 // activation, f32 residual, the position-embedding row add); anything else generic
 #define VTD_F32_CODES(X) X(0) X(1) X(2) X(8) X(9) X(10) X(EPI_RA)
@@ -1841,11 +1827,6 @@ void f32_pp2_launch(int M, int N, int K, const float* A, int lda, const float* B
   }
 }
 
-int gemm_launch(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
-                int dtype, const vtd_epilogue* epi, hipStream_t stream, double flops) {
-  return gemm_launch_ln(M, N, K, A, lda, Bt, ldb, dtype, epi, stream, flops, nullptr, 0, 0, 0.f);
-}
-
 // dtype VTD_BF16X3 (include/vtd.h "Split-bf16 operands"): a bf16 GEMM over K = 3 P whose A
 // rows are stored [hi | lo] (lda >= 2 P) and read as [hi | lo | hi] -- EpiArgs::aw = 2 P / 64
 // K-steps, after which the loop's A column returns to 0.  Returns aw (0: not split) and the
@@ -1857,12 +1838,8 @@ int split_a_wrap(int& dtype, int K, int lda) {
   return 2 * (K / 3) / 64;
 }
 
-// A GEMM whose LayerNorm-fold row statistics (epi->lnstat) are still the producer's partials
-// (lnpart, lnslots per row; the fold path): ln_stats_finalize first writes epi->lnstat.
-// lnpart == nullptr: a plain gemm_launch.
-int gemm_launch_ln(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
-                   int dtype, const vtd_epilogue* epi, hipStream_t stream, double flops,
-                   const float* lnpart, int lnslots, int lnD, float lneps) {
+int gemm_launch(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
+                int dtype, const vtd_epilogue* epi, hipStream_t stream, double flops) {
   VTD_CHECK_ARG(M > 0 && N > 0 && K > 0, "gemm: M, N, K must be positive");
   VTD_CHECK_ARG(K % VTD_KALIGN == 0, "gemm: K must be a multiple of VTD_KALIGN");
   VTD_CHECK_ARG(A && Bt && epi && epi->out, "gemm: null pointer");
@@ -1894,11 +1871,6 @@ int gemm_launch_ln(int M, int N, int K, const void* A, int lda, const void* Bt, 
   if (epi->statout && (split_a || !gemm_emits_stats(M, N, dtype, epi)))
     return fail(VTD_ERR_UNSUPPORTED, "gemm: statout needs full 256 x 256 tiles on the bf16 "
                                      "fast epilogues and bf16 operands (see gemm_emits_stats)");
-  if (lnpart) {
-    const int rc = ln_stats_finalize_launch(lnpart, M, lnslots, lnD, lneps,
-                                            const_cast<float*>(epi->lnstat), stream);
-    if (rc) return rc;
-  }
   ProfScope ps(stream, PROF_GEMM, flops > 0 ? flops : 2.0 * M * N * (double)K);
   const int tiles_m = (M + BBM - 1) / BBM, tiles_n = (N + BBN - 1) / BBN;
   // Kernel choice.  >= kMinBigTiles 256 x 256 tiles: pp2.  Fewer: the skinny kernel for

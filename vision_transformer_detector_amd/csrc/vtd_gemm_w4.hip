@@ -34,6 +34,7 @@
 
 #include "vtd_common.h"
 #include "vtd_gemm_epi.h"
+#include "vtd_launch.h"
 
 namespace vtd {
 
@@ -91,9 +92,6 @@ __device__ __forceinline__ void w4_sources(W4Src& s, const bf16_t* A, int lda, i
   }
 }
 
-#ifndef VTD_DIAG
-#define VTD_DIAG 0
-#endif
 // DG (VTD_DIAG builds only; timing diagnostics, WRONG outputs): bit 0 = no DMA after the
 // prologue (every K-step reads stale stages), bit 1 = every DMA re-fetches K-tile 0 (the
 // same instruction stream from L2-resident lines)

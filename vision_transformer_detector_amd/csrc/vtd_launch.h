@@ -1,0 +1,59 @@
+// The host launchers that one .hip file defines and another calls, declared once: every
+// file that defines or calls one includes this header, so a definition is checked against
+// its declaration.  Default arguments live here only.
+#pragma once
+
+#include "vtd_common.h"
+
+namespace vtd {
+
+// ----------------------------------------------------------------- vtd_gemm.hip
+int gemm_launch(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
+                int dtype, const vtd_epilogue* epi, hipStream_t stream, double flops);
+bool gemm_emits_stats(int M, int N, int dtype, const vtd_epilogue* e);
+int gemm_splitk_choice(int M, int N, int K, int dtype, int target = 0);
+int gemm_splitk_launch(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
+                       int dtype, const vtd_epilogue* epi, float* part, int ksplit,
+                       hipStream_t stream, double flops);
+bool gemm_mx8_emits_fp8(int M, int N, const vtd_epilogue* e);
+int gemm_mx8_launch(int M, int N, int K, const uint8_t* A, int lda, const uint8_t* sA,
+                    int64_t sa_rows, const uint8_t* Bt, int ldb, const uint8_t* sB,
+                    int64_t sb_rows, const vtd_epilogue* epi, hipStream_t stream,
+                    double flops);
+#if VTD_DIAG
+// vtd_gemm_w4.hip (diagnostic build only)
+bool gemm_w4_launch(int M, int N, int K, const bf16_t* A, int lda, const bf16_t* Bt, int ldb,
+                    const vtd_epilogue* epi, int ngw, hipStream_t stream);
+void gemm_mx8_x4_launch(int M, int N, int K, const uint8_t* A, int lda, const uint8_t* sA,
+                        int64_t sa_rows, const uint8_t* Bt, int ldb, const uint8_t* sB,
+                        int64_t sb_rows, const vtd_epilogue* epi, int ngw, hipStream_t stream);
+#endif
+
+// ----------------------------------------------------------------- vtd_attention.hip
+int attention_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
+                     float scale, void* out, int ldo, int dtype, hipStream_t stream,
+                     double flops, int parts = 1);
+int attention_mx8_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
+                         float scale, uint8_t* q, int ldq, uint8_t* s, int64_t s_rows,
+                         hipStream_t stream, double flops);
+
+// ----------------------------------------------------------------- vtd_elementwise.hip
+int layernorm_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx, const float* g,
+                     const float* b, float eps, void* y, int ldy, int dtype, hipStream_t st);
+int layernorm_mx8_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx,
+                         const float* g, const float* b, float eps, uint8_t* q, int ldq, int Kq,
+                         uint8_t* s, int64_t s_rows, hipStream_t st);
+int ln_stats_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx, float eps,
+                    float* stat, hipStream_t st);
+int ln_stats_finalize_launch(const float* part, int64_t rows, int slots, int D, float eps,
+                             float* stat, hipStream_t st);
+int patches_launch(const float* img, int B, int H, int W, int C, int p, void* out, int ldo,
+                   int dtype, hipStream_t st);
+int split_bf16x3_launch(const float* x, int64_t rows, int K, int ldx, void* y, int ldy, int role,
+                        hipStream_t st);
+
+// ----------------------------------------------------------------- vtd_mx8.hip
+int quantize_mx8_launch(const void* x, int x_dtype, int64_t rows, int K, int ldx, int Kq,
+                        uint8_t* q, int ldq, uint8_t* s, int64_t s_rows, hipStream_t st);
+
+}  // namespace vtd

@@ -11,7 +11,7 @@
 // tile's scales for a K-step as one contiguous 1-KiB block.
 #include <algorithm>
 
-#include "vtd_common.h"
+#include "vtd_launch.h"
 
 namespace vtd {
 

@@ -7,46 +7,9 @@
 #include <mutex>
 #include <vector>
 
-#include "vtd_common.h"
+#include "vtd_launch.h"
 
 namespace vtd {
-
-int gemm_launch(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
-                int dtype, const vtd_epilogue* epi, hipStream_t stream, double flops);
-int gemm_launch_ln(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
-                   int dtype, const vtd_epilogue* epi, hipStream_t stream, double flops,
-                   const float* lnpart, int lnslots, int lnD, float lneps);
-int attention_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
-                     float scale, void* out, int ldo, int dtype, hipStream_t stream,
-                     double flops, int parts = 1);
-int layernorm_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx, const float* g,
-                     const float* b, float eps, void* y, int ldy, int dtype, hipStream_t st);
-int ln_stats_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx, float eps,
-                    float* stat, hipStream_t st);
-int ln_stats_finalize_launch(const float* part, int64_t rows, int slots, int D, float eps,
-                             float* stat, hipStream_t st);
-bool gemm_emits_stats(int M, int N, int dtype, const vtd_epilogue* e);
-int gemm_splitk_choice(int M, int N, int K, int dtype, int target = 0);
-int gemm_splitk_launch(int M, int N, int K, const void* A, int lda, const void* Bt, int ldb,
-                       int dtype, const vtd_epilogue* epi, float* part, int ksplit,
-                       hipStream_t stream, double flops);
-int patches_launch(const float* img, int B, int H, int W, int C, int p, void* out, int ldo,
-                   int dtype, hipStream_t st);
-int attention_mx8_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
-                         float scale, uint8_t* q, int ldq, uint8_t* s, int64_t s_rows,
-                         hipStream_t stream, double flops);
-int quantize_mx8_launch(const void* x, int x_dtype, int64_t rows, int K, int ldx, int Kq,
-                        uint8_t* q, int ldq, uint8_t* s, int64_t s_rows, hipStream_t st);
-int layernorm_mx8_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx,
-                         const float* g, const float* b, float eps, uint8_t* q, int ldq, int Kq,
-                         uint8_t* s, int64_t s_rows, hipStream_t st);
-bool gemm_mx8_emits_fp8(int M, int N, const vtd_epilogue* e);
-int split_bf16x3_launch(const float* x, int64_t rows, int K, int ldx, void* y, int ldy, int role,
-                        hipStream_t st);
-int gemm_mx8_launch(int M, int N, int K, const uint8_t* A, int lda, const uint8_t* sA,
-                    int64_t sa_rows, const uint8_t* Bt, int ldb, const uint8_t* sB,
-                    int64_t sb_rows, const vtd_epilogue* epi, hipStream_t stream,
-                    double flops);
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_last_error;
@@ -201,34 +164,94 @@ static int derive(const vtd_config* c, vtd_dims* d) {
 }
 
 namespace {
+// The environment switches of the forward, read once per process on first use (A/B and
+// diagnostic settings; the run-time knobs above are the ones a caller can change).
+struct Switches {
+  bool resid_f32;       // VTD_RESID_F32=1: f32 residual stream in the bf16 modes (Mode::resid)
+  bool split_pad;       // VTD_SPLIT_PAD=0: the parts of a split forward do not pad their rows
+  int split_min_tiles;  // VTD_SPLIT_MIN_TILES: fewest 256-row tiles per part (split_parts)
+  int streams;          // VTD_STREAMS: most micro-batch parts, clamped to [1, kMaxSplit]; 1 = off
+  bool ln_partials;     // VTD_LN_PARTIALS=0: row-statistics pass instead of producer partials
+  bool enc_splitk;      // VTD_ENC_SPLITK=0: no split-K of the encoder's Dense layers (A/B)
+#if VTD_DIAG
+  // VTD_DIAG builds only (timing diagnostics, WRONG outputs): VTD_DIAG_NOFIN skips the
+  // LayerNorm finalize launches, VTD_DIAG_NOATTN the attention launches, VTD_DIAG_NOHEAD
+  // the detection head
+  // (VTD_DIAG_NOFIN=n: after the first n finalize launches, so the consumers keep applying
+  // the last real row statistics: activations stay realistic, MFMA power and clock with them)
+  int diag_nofin;
+  bool diag_noattn, diag_nohead;
+#else
+  static constexpr int diag_nofin = -1;
+  static constexpr bool diag_noattn = false, diag_nohead = false;
+#endif
+};
+constexpr int kMaxSplit = 4;        // most micro-batch parts of one forward
+const Switches& switches() {
+  static const Switches sw = [] {
+    auto num = [](const char* name, int unset) {
+      const char* v = getenv(name);
+      return v ? atoi(v) : unset;
+    };
+    Switches s{};
+    s.resid_f32 = num("VTD_RESID_F32", 0) != 0;
+    s.split_pad = num("VTD_SPLIT_PAD", 1) != 0;
+    s.split_min_tiles = std::max(1, num("VTD_SPLIT_MIN_TILES", 24));
+    s.streams = std::min(std::max(num("VTD_STREAMS", 2), 1), kMaxSplit);
+    s.ln_partials = num("VTD_LN_PARTIALS", 1) != 0;
+    s.enc_splitk = num("VTD_ENC_SPLITK", 1) != 0;
+#if VTD_DIAG
+    s.diag_nofin = num("VTD_DIAG_NOFIN", -1);
+    s.diag_noattn = getenv("VTD_DIAG_NOATTN") != nullptr;
+    s.diag_nohead = getenv("VTD_DIAG_NOHEAD") != nullptr;
+#endif
+    return s;
+  }();
+  return sw;
+}
+// What a vtd_config.dtype means for the forward's buffers and GEMMs.
+struct Mode {
+  // activation / non-MX matrix dtype (VTD_FP8 keeps everything else in bf16; the split-bf16
+  // mode VTD_BF16X3 keeps its activations -- query/key/value, attention -- in f32)
+  int act;
+  // GEMM operand dtype.  VTD_BF16X3: every GEMM runs on split-bf16 operands (bf16 kernels over
+  // K' = 3 K_p, A rows stored [hi | lo], 2 K_p wide), which the producers write directly
+  int op;
+  // dtype of the residual stream x: bf16 in the bf16 / fp8 modes (the stream the GEMM
+  // epilogues add into and the LayerNorms read), f32 in the f32 mode.  VTD_RESID_F32=1
+  // keeps an f32 stream in the bf16 modes (A/B diagnostic; costs ~7 % at C2).
+  int resid;
+  // bytes per element of an activation (es) and per logical element of a GEMM A operand --
+  // patches, LayerNorm out, MLP / head activations (eop; VTD_BF16X3: the pieces [hi | lo])
+  size_t es, eop;
+  bool fp8, x3;
+  // stored width of a K-wide logical A row, and the GEMM's K (the weights' row width) for it
+  int ka(int k) const { return x3 ? 2 * k : k; }
+  int kk(int k) const { return x3 ? 3 * k : k; }
+};
+Mode mode_of(int dtype) {
+  Mode m{};
+  m.fp8 = dtype == VTD_FP8;
+  m.x3 = dtype == VTD_BF16X3;
+  m.act = m.fp8 ? VTD_BF16 : m.x3 ? VTD_F32 : dtype;
+  m.op = m.x3 ? VTD_BF16X3 : m.act;
+  m.resid = m.act == VTD_BF16 && !switches().resid_f32 ? VTD_BF16 : VTD_F32;
+  m.es = m.act == VTD_BF16 ? 2 : 4;
+  m.eop = m.x3 ? 4 : m.es;
+  return m;
+}
+// Workspace offsets of one part, and the split-K counts its buffers were sized for: the
+// forward launches with exactly these (1 = no split).
 struct Plan {
-  size_t patches, x, xb, h, stat, pstat, qkv, attn, attn3, mlp0, mlp1, u, head0, head1, q8, s8, q8b,
+  size_t patches, x, xb, h, stat, pstat, qkv, attn, mlp0, mlp1, u, head0, head1, q8, s8, q8b,
       s8b, splitk, splitk_bytes, total;
   int k8_max;                       // widest MX-fp8 GEMM K (VTD_FP8)
   int64_t s8_rows;                  // activation scale rows (rows rounded up to 4)
+  int head_ks[VTD_MAX_HEAD];        // per head layer (gemm_splitk_choice)
+  // per encoder Dense role (enc_splitk_choice), before "a GEMM that writes partial
+  // statistics does not split" (Part::enc_gemm)
+  int qkv_ks, out_ks, mlp_ks[VTD_MAX_MLP];
 };
-// activation / non-MX matrix dtype of a mode (VTD_FP8 keeps everything else in bf16; the
-// split-bf16 mode VTD_BF16X3 keeps its activations -- query/key/value, attention -- in f32)
-int act_dtype(int dtype) {
-  return dtype == VTD_FP8 ? VTD_BF16 : dtype == VTD_BF16X3 ? VTD_F32 : dtype;
-}
-size_t es_of(int dtype) { return act_dtype(dtype) == VTD_BF16 ? 2 : 4; }
-// GEMM A operands (patches, LayerNorm out, MLP / head activations): bytes per logical element
-// (VTD_BF16X3: the two bf16 pieces [hi | lo]) and the stored width of a K-wide logical row;
-// opk: the GEMM's K (and the weights' row width) for it (VTD_BF16X3: K' = 3 K)
-size_t eop_of(int dtype) { return dtype == VTD_BF16X3 ? 4 : es_of(dtype); }
-int opa(int dtype, int k) { return dtype == VTD_BF16X3 ? 2 * k : k; }
-int opk(int dtype, int k) { return dtype == VTD_BF16X3 ? 3 * k : k; }
-// dtype of the residual stream x: bf16 in the bf16 / fp8 modes (the stream the GEMM
-// epilogues add into and the LayerNorms read), f32 in the f32 mode.  VTD_RESID_F32=1
-// keeps an f32 stream in the bf16 modes (A/B diagnostic; costs ~7 % at C2).
-int resid_dtype(int dtype) {
-  static const bool f32 = [] {
-    const char* v = getenv("VTD_RESID_F32");
-    return v && atoi(v) != 0;
-  }();
-  return act_dtype(dtype) == VTD_BF16 && !f32 ? VTD_BF16 : VTD_F32;
-}
 int k8_of(int k) { return (int)round_up(k, 128); }
 // Encoder rows of a micro-batch part: a part's batch x tokens rounded up to whole 256-row
 // tiles (pad), so that every encoder GEMM of the part runs full tiles -- the fast epilogues
@@ -236,18 +259,12 @@ int k8_of(int k) { return (int)round_up(k, 128); }
 // on the generic epilogue (C2 at B = 64 in two parts of 32 images: 6272 rows -> 6400).  The
 // pad rows start from zero patches; rows never mix in a GEMM, LayerNorm or the attention
 // (which reads the real images' rows only), and the head reads the real rows only.
-int64_t gemm_rows(const vtd_dims& d, bool pad) { return pad ? round_up(d.rows, 256) : d.rows; }
-// whether the parts of a split forward pad their rows (VTD_SPLIT_PAD=0: not, A/B only)
-bool split_pad() {
-  static const bool on = [] {
-    const char* v = getenv("VTD_SPLIT_PAD");
-    return !v || atoi(v) != 0;
-  }();
-  return on;
+// Only the parts of a split forward pad (nparts > 1), and not with VTD_SPLIT_PAD=0.
+int64_t gemm_rows(const vtd_dims& d, int nparts) {
+  return nparts > 1 && switches().split_pad ? round_up(d.rows, 256) : d.rows;
 }
-// pad: the encoder runs on rows rounded up to whole 256-row GEMM tiles (gemm_rows)
 // nparts: the micro-batch parts running concurrently (each part's encoder rows are padded
-// when > 1, split_pad; its head's split-K launches target 256 / nparts workgroups, since the
+// when > 1, gemm_rows; its head's split-K launches target 256 / nparts workgroups, since the
 // parts' head launches co-run: +0.2 % at C2 B = 256, +0.9 % at B = 64,
 // profiles/r05_splitk_target_ab.log)
 int splitk_target(int nparts) { return 256 / std::max(nparts, 1); }
@@ -280,8 +297,7 @@ int enc_splitk_choice(int64_t M, int N, int K, int nparts, int dtype, size_t max
   }
   return bs;
 }
-Plan make_plan(const vtd_config* c, const vtd_dims& d, int nparts = 1) {
-  const bool pad = nparts > 1 && split_pad();
+Plan make_plan(const vtd_config* c, const vtd_dims& d, const Mode& m, int nparts = 1) {
   Plan p{};
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -289,22 +305,21 @@ Plan make_plan(const vtd_config* c, const vtd_dims& d, int nparts = 1) {
     off += (bytes + 255) / 256 * 256;
     return o;
   };
-  const size_t es = es_of(c->dtype), eop = eop_of(c->dtype);
-  const size_t R = (size_t)gemm_rows(d, pad), HR = (size_t)d.head_rows;
+  const size_t es = m.es, eop = m.eop;
+  const size_t R = (size_t)gemm_rows(d, nparts), HR = (size_t)d.head_rows;
   int mlp_max = 0, head_max = 0;
   for (int j = 0; j < c->mlp_quantities; ++j) mlp_max = std::max(mlp_max, d.mlp_units_p[j]);
   for (int j = 0; j < d.n_head; ++j) head_max = std::max(head_max, d.head_units_p[j]);
   p.patches = take(R * d.patch_dim_p * eop);
   p.x = take(R * d.d_p * 4);
-  p.xb = take(act_dtype(c->dtype) == VTD_BF16 ? R * d.d_p * 2 : 0);
+  p.xb = take(m.act == VTD_BF16 ? R * d.d_p * 2 : 0);
   p.h = take(R * d.d_p * eop);
   p.stat = take(R * 8);                 // LayerNorm (mean, rstd) per row, fold path
   p.pstat = take(R * (d.d_p / 64) * 8);  // producer partial (sum, sumsq) per 64 columns
   p.qkv = take(R * d.qkv_p * es);
   // the attention output; VTD_BF16X3: written by the attention kernel as the split-bf16
-  // operand of attention_output (attn3), no f32 copy
-  p.attn = take(c->dtype == VTD_BF16X3 ? 0 : R * d.inner_p * es);
-  p.attn3 = take(c->dtype == VTD_BF16X3 ? R * d.inner_p * eop : 0);
+  // operand of attention_output, no f32 copy
+  p.attn = take(R * d.inner_p * (m.x3 ? eop : es));
   p.mlp0 = take(R * mlp_max * eop);
   p.mlp1 = take(R * mlp_max * eop);
   p.u = take(HR * d.tokens_p * eop);
@@ -313,20 +328,28 @@ Plan make_plan(const vtd_config* c, const vtd_dims& d, int nparts = 1) {
   // fp32 split-K partials of the head's few-tile, long-K Dense layers (gemm_splitk_choice)
   size_t sk = 0;
   for (int j = 0, k = d.tokens_p; j < d.n_head; k = d.head_units_p[j], ++j) {
-    const int s = gemm_splitk_choice((int)HR, d.head_units_p[j], opk(c->dtype, k),
-                                     c->dtype == VTD_BF16X3 ? VTD_BF16X3 : act_dtype(c->dtype),
-                                     splitk_target(nparts));
+    const int s = p.head_ks[j] = gemm_splitk_choice((int)HR, d.head_units_p[j], m.kk(k), m.op,
+                                                    splitk_target(nparts));
     if (s > 1) sk = std::max(sk, (size_t)s * HR * d.head_units_p[j] * 4);
   }
-  // and of the encoder's few-tile Dense layers (small batches, enc_gemm; bf16 operands): a
-  // fixed reserve, whose size bounds their split counts (enc_splitk_choice)
-  if (c->dtype == VTD_BF16 || c->dtype == VTD_BF16X3) sk = std::max(sk, kEncSplitBytes);
+  // and of the encoder's few-tile Dense layers (small batches, Part::enc_gemm; bf16 operands):
+  // a fixed reserve, whose size bounds their split counts (enc_splitk_choice)
+  const bool enc = !m.fp8 && m.op != VTD_F32;
+  if (enc) sk = std::max(sk, kEncSplitBytes);
   p.splitk_bytes = sk;
   p.splitk = take(sk);
+  auto enc_ks = [&](int N, int K) {
+    return enc && switches().enc_splitk
+               ? enc_splitk_choice((int64_t)R, N, m.kk(K), nparts, m.op, p.splitk_bytes) : 1;
+  };
+  p.qkv_ks = enc_ks(d.qkv_p, d.d_p);
+  p.out_ks = enc_ks(d.d_p, d.inner_p);
+  for (int j = 0, k = d.d_p; j < c->mlp_quantities; k = d.mlp_units_p[j], ++j)
+    p.mlp_ks[j] = enc_ks(d.mlp_units_p[j], k);
   // VTD_FP8: one MX-fp8 copy of the current encoder GEMM's A operand + its scales
   p.k8_max = 0;
   p.s8_rows = round_up((int64_t)R, 4);
-  if (c->dtype == VTD_FP8) {
+  if (m.fp8) {
     p.k8_max = std::max(k8_of(d.d_p), k8_of(d.inner_p));
     for (int j = 0; j + 1 < c->mlp_quantities; ++j) p.k8_max = std::max(p.k8_max, k8_of(d.mlp_units_p[j]));
   }
@@ -344,24 +367,13 @@ Plan make_plan(const vtd_config* c, const vtd_dims& d, int nparts = 1) {
 // tiles of an N = 768 layer = 2.3 rounds of 256 CUs) runs beside the other half's work
 // instead of leaving CUs idle.  VTD_STREAMS=1 disables it; so does per-kernel profiling
 // (vtd_profile_enable): each profiled launch then runs alone and its events time it.
-constexpr int kMaxSplit = 4;   // VTD_STREAMS is clamped to [1, kMaxSplit]
-// fewest 256-row tiles per part (VTD_SPLIT_MIN_TILES; C2 at B = 256, 2 parts: 98 each; at
-// B = 64, 2 parts of 24.5 tiles padded to 25: +15 % over one stream since round 5, once the
-// parts' 75-tile layers run the 256-tile kernels, profiles/r05_b64_split_ab.log)
-int split_min_tiles() {
-  static const int t = [] {
-    const char* v = getenv("VTD_SPLIT_MIN_TILES");
-    return v ? std::max(1, atoi(v)) : 24;
-  }();
-  return t;
-}
+// Fewest 256-row tiles per part: VTD_SPLIT_MIN_TILES, default 24 (C2 at B = 256, 2 parts: 98
+// each; at B = 64, 2 parts of 24.5 tiles padded to 25: +15 % over one stream since round 5, once
+// the parts' 75-tile layers run the 256-tile kernels, profiles/r05_b64_split_ab.log)
 int split_parts(const vtd_config* c, const vtd_dims& d) {
-  static const int streams = [] {
-    const char* v = getenv("VTD_STREAMS");
-    return v ? atoi(v) : 2;
-  }();
-  int ns = std::min(std::max(streams, 1), (int)kMaxSplit);
-  while (ns > 1 && (c->batch < ns || d.rows < (int64_t)ns * split_min_tiles() * 256)) --ns;
+  const Switches& sw = switches();
+  int ns = sw.streams;
+  while (ns > 1 && (c->batch < ns || d.rows < (int64_t)ns * sw.split_min_tiles * 256)) --ns;
   return ns;
 }
 int split_count(const vtd_config* c, const vtd_dims& d) {
@@ -375,17 +387,16 @@ vtd_config sub_config(const vtd_config* c, int part, int nsplit) {
 }
 // workspace of either form (profiling can toggle between them)
 size_t split_workspace(const vtd_config* c, const vtd_dims& d) {
-  const size_t whole = make_plan(c, d).total;
-  vtd_dims dd;
-  if (derive(c, &dd) != VTD_OK) return 0;
-  const int ns = split_parts(c, dd);
+  const Mode m = mode_of(c->dtype);
+  const size_t whole = make_plan(c, d, m).total;
+  const int ns = split_parts(c, d);
   if (ns == 1) return whole;
   size_t total = 0;
   for (int i = 0; i < ns; ++i) {
     const vtd_config sc = sub_config(c, i, ns);
     vtd_dims sd;
     if (derive(&sc, &sd) != VTD_OK) return 0;
-    total += make_plan(&sc, sd, ns).total;
+    total += make_plan(&sc, sd, m, ns).total;
   }
   return std::max(total, whole);
 }
@@ -424,15 +435,294 @@ SideStream* side_stream(hipStream_t st) {
   return &ss;
 }
 
-// Stages of one forward: 0 = patches + linear projection, 1..L = encoder layer s - 1,
-// L + 1 = head + decode.  forward_impl runs stages [s_lo, s_hi); `partials` carries
-// "the GEMM that last wrote x emitted LayerNorm partials" from one stage to the next.
+// One micro-batch part of a forward (the whole batch when the forward is not split): its
+// shapes, mode, workspace plan, typed buffers and stream, built once per vtd_forward, and its
+// stages as functions.  Stages: 0 = patches + linear projection (embed), 1..L = encoder layer
+// s - 1, L + 1 = head + decode.  `partials` carries "the GEMM that last wrote x emitted
+// LayerNorm partials" from one stage to the next.
 // nparts: the micro-batch parts of the forward (workspace plan, row padding, head split-K);
 // nconc: how many of them run concurrently (nparts, or 1 when they run one after another on
 // the caller's stream: a first call under graph capture) -- the persistent attention's grid
-int forward_impl(const vtd_config* cfg, const vtd_weights* w, const float* images,
-                 float* logits, float* dets, char* ws, hipStream_t st, int s_lo, int s_hi,
-                 bool& partials, int nparts, int nconc);
+struct Part {
+  vtd_config cfg;
+  vtd_dims d;
+  Mode m;
+  Plan P;
+  const vtd_weights* w;
+  const float* images;
+  float *logits, *dets;
+  hipStream_t st;
+  int nparts, nconc;
+  int64_t R; int M;          // the encoder's rows (gemm_rows: whole 256-row tiles of a part)
+  int act;                   // the Dense layers' activation
+  double fR;                 // algorithmic FLOPs: the real rows
+  bool partials;
+  void *patches, *x, *xb, *h, *qkv, *attn, *mlp[2], *u, *hd[2];
+  float *stat, *pstat, *splitk;
+  uint8_t *q8, *s8, *q8b, *s8b;     // VTD_FP8: the two MX-fp8 operand buffers + scales
+
+  int init(const vtd_config& c, const vtd_weights* w, const float* images, float* logits,
+           float* dets, char* ws, hipStream_t st, int nparts, int nconc);
+  int stage(int s) { return s == 0 ? embed() : s <= cfg.repeat_times ? layer(s - 1) : head(); }
+  int embed();
+  int layer(int i);                       // attention block, then mlp_stack(i)
+  int mlp_stack(int i);
+  int head();
+  void emit_stats(vtd_epilogue& e, bool next_fold);
+  int row_stats();
+  int layernorm(const float* g, const float* b);
+  int enc_gemm(int Np, int K, int ks, const void* a, const void* W, const uint8_t* S,
+               const vtd_epilogue* e, double flops);
+  int mx_gemm(int Np, int K, const uint8_t* qa, const uint8_t* sa, const void* W,
+              const uint8_t* S, const vtd_epilogue* e, double flops);
+};
+
+int Part::init(const vtd_config& c, const vtd_weights* w_, const float* images_, float* logits_,
+               float* dets_, char* ws, hipStream_t st_, int nparts_, int nconc_) {
+  cfg = c; w = w_; images = images_; logits = logits_; dets = dets_; st = st_;
+  nparts = nparts_; nconc = nconc_;
+  if (int rc = derive(&cfg, &d)) return rc;
+  m = mode_of(cfg.dtype);
+  P = make_plan(&cfg, d, m, nparts);
+  R = gemm_rows(d, nparts);
+  VTD_CHECK_ARG(R < (int64_t)1 << 31, "forward: batch*tokens too large");
+  M = (int)R;
+  act = cfg.use_mish ? VTD_ACT_MISH : VTD_ACT_GELU_TANH;
+  fR = (double)d.rows;
+  partials = false;
+  patches = ws + P.patches; x = ws + P.x; xb = ws + P.xb; h = ws + P.h; qkv = ws + P.qkv;
+  attn = ws + P.attn; mlp[0] = ws + P.mlp0; mlp[1] = ws + P.mlp1; u = ws + P.u;
+  hd[0] = ws + P.head0; hd[1] = ws + P.head1;
+  stat = reinterpret_cast<float*>(ws + P.stat);
+  pstat = reinterpret_cast<float*>(ws + P.pstat);
+  splitk = reinterpret_cast<float*>(ws + P.splitk);
+  q8 = reinterpret_cast<uint8_t*>(ws + P.q8); s8 = reinterpret_cast<uint8_t*>(ws + P.s8);
+  q8b = reinterpret_cast<uint8_t*>(ws + P.q8b); s8b = reinterpret_cast<uint8_t*>(ws + P.s8b);
+  return VTD_OK;
+}
+
+// fold path: the GEMM writing x emits partial row statistics when it can (full tiles on
+// the bf16 fast epilogues); the LayerNorm point then only finalizes them (`partials`)
+void Part::emit_stats(vtd_epilogue& e, bool next_fold) {
+  partials = false;
+  // centred per-block partials need every 64-column block full of valid columns
+  if (!next_fold || m.fp8 || m.act != VTD_BF16 || !switches().ln_partials || d.d != d.d_p) return;
+  e.statout = pstat; e.stat_ld = (int)R;       // slot-major planes of R rows
+  partials = gemm_emits_stats(M, d.d_p, m.act, &e);
+  if (!partials) { e.statout = nullptr; e.stat_ld = 0; }
+}
+int Part::row_stats() {
+  static std::atomic<int> diag_fin_count{0};
+  if (switches().diag_nofin >= 0 && partials &&
+      diag_fin_count.fetch_add(1) >= switches().diag_nofin) return VTD_OK;
+  return partials ? ln_stats_finalize_launch(pstat, R, d.d_p / 64, d.d, 1e-3f, stat, st)
+                  : ln_stats_launch(x, m.resid, R, d.d, d.d_p, 1e-3f, stat, st);
+}
+// LayerNorm of x as the next GEMM's A operand: into h, or in VTD_FP8 mode straight into the
+// MX-fp8 operand buffer q8 / s8 (LayerNorm + MX quantization, one pass)
+int Part::layernorm(const float* g, const float* b) {
+  const int D = d.d, Dp = d.d_p;
+  if (m.fp8)
+    return layernorm_mx8_launch(x, m.resid, R, D, Dp, g, b, 1e-3f, q8, k8_of(Dp), k8_of(Dp), s8,
+                                P.s8_rows, st);
+  return layernorm_launch(x, m.resid, R, D, Dp, g, b, 1e-3f, h, m.ka(Dp), m.op, st);
+}
+// encoder Dense layer (query/key/value, attention_output, MLP): bf16/f32 GEMM, or in
+// VTD_FP8 mode MX-fp8 quantization of the bf16 A operand + the block-scaled MFMA GEMM
+// against the MX-fp8 weights (W [Np][K8], S [K8/128][Np][4])
+int Part::enc_gemm(int Np, int K, int ks, const void* a, const void* W, const uint8_t* S,
+                   const vtd_epilogue* e, double flops) {
+  if (!m.fp8) {
+    // few-tile, long-K layers (small batches) split K (ks: the plan's count for this layer);
+    // not with partial statistics, which the split-K epilogue does not write
+    if (ks > 1 && !e->statout)
+      return gemm_splitk_launch(M, Np, m.kk(K), a, m.ka(K), W, m.kk(K), m.op, e, splitk, ks, st,
+                                flops);
+    return gemm_launch(M, Np, m.kk(K), a, m.ka(K), W, m.kk(K), m.op, e, st, flops);
+  }
+  const int K8 = k8_of(K);
+  int r = quantize_mx8_launch(a, VTD_BF16, R, K, K, K8, q8, K8, s8, P.s8_rows, st);
+  if (r) return r;
+  return mx_gemm(Np, K, q8, s8, W, S, e, flops);
+}
+// VTD_FP8: the GEMM on an operand a producer already wrote as MX-fp8 (qa, sa)
+int Part::mx_gemm(int Np, int K, const uint8_t* qa, const uint8_t* sa, const void* W,
+                  const uint8_t* S, const vtd_epilogue* e, double flops) {
+  const int K8 = k8_of(K);
+  return gemm_mx8_launch(M, Np, K8, qa, K8, sa, P.s8_rows, static_cast<const uint8_t*>(W), K8,
+                         S, Np, e, st, flops);
+}
+
+int Part::embed() {
+  const int Dp = d.d_p;
+  // ---- ExtractImagePatches + flatten (vtd.py:271-280)
+  int rc = patches_launch(images, cfg.batch, cfg.image_h, cfg.image_w, cfg.channels,
+                          cfg.patch_size, patches, m.ka(d.patch_dim_p), m.op, st);
+  if (rc) return rc;
+  if (R > d.rows) {                                   // pad rows: zero patches
+    const size_t row_bytes = (size_t)d.patch_dim_p * m.eop;
+    VTD_HIP(hipMemsetAsync(static_cast<char*>(patches) + (size_t)d.rows * row_bytes, 0,
+                           (size_t)(R - d.rows) * row_bytes, st));
+    // and the attention output's pad rows, which the attention never writes
+    const size_t attn_row = (size_t)d.inner_p * (m.x3 ? m.eop : m.es);
+    VTD_HIP(hipMemsetAsync(static_cast<char*>(attn) + (size_t)d.rows * attn_row, 0,
+                           (size_t)(R - d.rows) * attn_row, st));
+  }
+  // ---- linear_projection + position embedding add (vtd.py:291-307)
+  vtd_epilogue e{};
+  e.bias = w->b_patch;
+  e.rowadd = w->pos_embedding; e.rowadd_period = d.tokens; e.rowadd_ncols = d.d;
+  e.act = VTD_ACT_NONE;
+  e.out = x; e.ldo = Dp; e.out_dtype = m.resid;
+  emit_stats(e, cfg.repeat_times > 0 && w->layers[0].ln1_colsum);
+  return gemm_launch(M, Dp, m.kk(d.patch_dim_p), patches, m.ka(d.patch_dim_p), w->w_patch,
+                     m.kk(d.patch_dim_p), m.op, &e, st, 2.0 * fR * d.d * d.patch_dim);
+}
+
+int Part::layer(int i) {                               // vtd.py:350-412
+  const vtd_layer_weights& L = w->layers[i];
+  const bool fp8 = m.fp8, x3 = m.x3;
+  const int dt = m.act, rdt = m.resid, B = cfg.batch, N = d.tokens, D = d.d, Dp = d.d_p;
+  if ((fp8 || x3) && (L.ln1_colsum || L.ln2_colsum))
+    return fail(VTD_ERR_UNSUPPORTED, "forward: LayerNorm fold (ln*_colsum) is not supported in "
+                                     "the VTD_FP8 / VTD_BF16X3 modes");
+  // the folded GEMMs take the residual stream x itself as their A operand (read in dt)
+  if (rdt != dt && (L.ln1_colsum || L.ln2_colsum))
+    return fail(VTD_ERR_UNSUPPORTED, "forward: LayerNorm fold (ln*_colsum) needs the residual "
+                                     "stream in the compute dtype (unset VTD_RESID_F32)");
+  // LayerNorm 1: its own pass into h (VTD_FP8: q8 / s8), or folded into the query/key/value GEMM
+  int rc = L.ln1_colsum ? row_stats() : layernorm(L.ln1_gamma, L.ln1_beta);
+  if (rc) return rc;
+  {
+    vtd_epilogue e{};
+    e.bias = L.b_qkv; e.act = VTD_ACT_NONE;
+    e.out = qkv; e.ldo = d.qkv_p; e.out_dtype = dt;
+    if (L.ln1_colsum) { e.lnstat = stat; e.colsum = L.ln1_colsum; }
+    const double fl = 2.0 * fR * D * 3.0 * cfg.num_heads * cfg.key_dim;
+    rc = fp8 ? mx_gemm(d.qkv_p, Dp, q8, s8, L.w_qkv, L.s_qkv, &e, fl)
+             : enc_gemm(d.qkv_p, Dp, P.qkv_ks, L.ln1_colsum ? x : h, L.w_qkv, L.s_qkv, &e, fl);
+    if (rc) return rc;
+  }
+  // VTD_FP8 with whole MX K-steps: attention writes the output GEMM's MX-fp8 operand
+  // VTD_BF16X3: the attention writes the attention_output GEMM's split-bf16 operand itself
+  const bool attn_mx8 = fp8 && d.inner_p % 128 == 0 && k8_of(d.inner_p) == d.inner_p;
+  const float scale = 1.0f / std::sqrt((float)cfg.key_dim);
+  const double attn_flops = 4.0 * B * cfg.num_heads * (double)N * N * cfg.key_dim;
+  rc = switches().diag_noattn ? VTD_OK
+       : attn_mx8 ? attention_mx8_launch(qkv, B, N, cfg.num_heads, d.key_dim_p, d.qkv_p, scale,
+                                         q8, d.inner_p, s8, P.s8_rows, st, attn_flops)
+                  : attention_launch(qkv, B, N, cfg.num_heads, d.key_dim_p, d.qkv_p, scale, attn,
+                                     m.ka(d.inner_p), m.op, st, attn_flops, nconc);
+  if (rc) return rc;
+  {
+    vtd_epilogue e{};
+    e.bias = L.b_out; e.act = VTD_ACT_NONE;
+    e.resid = x; e.ldr = Dp;
+    e.out = x; e.ldo = Dp; e.out_dtype = rdt;
+    emit_stats(e, L.ln2_colsum != nullptr);
+    const double fl = 2.0 * fR * cfg.num_heads * cfg.key_dim * D;
+    rc = attn_mx8 ? mx_gemm(Dp, d.inner_p, q8, s8, L.w_out, L.s_out, &e, fl)
+                  : enc_gemm(Dp, d.inner_p, P.out_ks, attn, L.w_out, L.s_out, &e, fl);
+    if (rc) return rc;
+  }
+  return mlp_stack(i);
+}
+
+int Part::mlp_stack(int i) {
+  const vtd_layer_weights& L = w->layers[i];
+  const bool fp8 = m.fp8;
+  const int dt = m.act, rdt = m.resid, D = d.d, Dp = d.d_p;
+  // LayerNorm 2, as LayerNorm 1.  VTD_FP8: the current MLP operand as MX-fp8 (aq, as), written
+  // by its producer
+  int rc = L.ln2_colsum ? row_stats() : layernorm(L.ln2_gamma, L.ln2_beta);
+  if (rc) return rc;
+  const void* a = L.ln2_colsum ? x : h;
+  const uint8_t* aq = fp8 && !L.ln2_colsum ? q8 : nullptr;
+  const uint8_t* as = aq ? s8 : nullptr;
+  const int q = cfg.mlp_quantities;
+  int k = Dp, kv = D;
+  for (int j = 0; j < q; ++j) {
+    const bool last = j == q - 1;
+    vtd_epilogue e{};
+    e.bias = L.b_mlp[j]; e.act = act;
+    if (j == 0 && L.ln2_colsum) { e.lnstat = stat; e.colsum = L.ln2_colsum; }
+    if (last) {
+      e.resid = x; e.ldr = Dp;
+      e.out = x; e.ldo = Dp; e.out_dtype = rdt;
+      if (i == cfg.repeat_times - 1 && dt == VTD_BF16 && rdt == VTD_F32) {
+        e.out2 = xb; e.ldo2 = Dp;           // bf16 copy of an f32 stream for the head
+      }
+      emit_stats(e, i + 1 < cfg.repeat_times && w->layers[i + 1].ln1_colsum);
+    } else {
+      e.out = mlp[j & 1]; e.ldo = m.ka(d.mlp_units_p[j]); e.out_dtype = m.op;
+    }
+    // VTD_FP8: an inner MLP layer writes the next layer's MX-fp8 operand itself (into the
+    // operand buffer it is not reading) when every tile takes the fast epilogue
+    uint8_t *nq = nullptr, *ns = nullptr;
+    if (fp8 && !last) {
+      nq = aq == q8b ? q8 : q8b;        // (enc_gemm quantizes into q8)
+      ns = aq == q8b ? s8 : s8b;
+      vtd_epilogue ef = e;
+      ef.out = nq; ef.ldo = k8_of(d.mlp_units_p[j]); ef.out_dtype = VTD_FP8;
+      ef.scale_out = ns; ef.scale_rows = P.s8_rows;
+      if (gemm_mx8_emits_fp8(M, d.mlp_units_p[j], &ef)) e = ef;
+      else nq = ns = nullptr;
+    }
+    const double fl = 2.0 * fR * kv * d.mlp_units[j];
+    rc = aq ? mx_gemm(d.mlp_units_p[j], k, aq, as, L.w_mlp[j], L.s_mlp[j], &e, fl)
+            : enc_gemm(d.mlp_units_p[j], k, P.mlp_ks[j], a, L.w_mlp[j], L.s_mlp[j], &e, fl);
+    if (rc) return rc;
+    a = mlp[j & 1]; aq = nq; as = ns;
+    k = d.mlp_units_p[j]; kv = d.mlp_units[j];
+  }
+  return VTD_OK;
+}
+
+int Part::head() {
+  if (switches().diag_nohead) return VTD_OK;
+  const int N = d.tokens, D = d.d, Dp = d.d_p, HR = (int)d.head_rows, gdt = m.op;
+  int rc;
+  // ---- mlp_head: Dense(17) + Reshape((17, -1)) as a scatter epilogue (vtd.py:454-463)
+  {
+    VTD_HIP(hipMemsetAsync(u, 0, (size_t)d.head_rows * d.tokens_p * m.eop, st));
+    vtd_epilogue e{};
+    e.bias = w->b_det; e.act = VTD_ACT_NONE;
+    e.out = u; e.ldo = m.ka(d.tokens_p); e.out_dtype = m.op;
+    e.scatter_tokens = N;
+    const void* a = m.act == m.resid ? x : xb;
+    if (m.x3) {                      // the f32 stream x as the split-bf16 operand (h is free)
+      rc = split_bf16x3_launch(static_cast<const float*>(x), R, Dp, Dp, h, m.ka(Dp), 0, st);
+      if (rc) return rc;
+      a = h;
+    }
+    // the real rows only (the scatter addresses images by row)
+    rc = gemm_launch((int)d.rows, VTD_MAX_DETECT, m.kk(Dp), a, m.ka(Dp), w->w_det, m.kk(Dp), gdt,
+                     &e, st, 2.0 * fR * D * VTD_MAX_DETECT);
+    if (rc) return rc;
+  }
+  const void* a = u;
+  int k = d.tokens_p, kv = N;
+  for (int j = 0; j < d.n_head; ++j) {                // vtd.py:468-486
+    vtd_epilogue e{};
+    e.bias = w->b_head[j]; e.act = act;
+    e.out = hd[j & 1]; e.ldo = m.ka(d.head_units_p[j]); e.out_dtype = m.op;
+    const double fl = 2.0 * HR * (double)kv * d.head_units[j];
+    const int ks = P.head_ks[j];
+    rc = ks > 1 ? gemm_splitk_launch(HR, d.head_units_p[j], m.kk(k), a, m.ka(k), w->w_head[j],
+                                     m.kk(k), gdt, &e, splitk, ks, st, fl)
+                : gemm_launch(HR, d.head_units_p[j], m.kk(k), a, m.ka(k), w->w_head[j], m.kk(k),
+                              gdt, &e, st, fl);
+    if (rc) return rc;
+    a = hd[j & 1];
+    k = d.head_units_p[j]; kv = d.head_units[j];
+  }
+  vtd_epilogue e{};                                   // MLP_Head_no_Sigmoid vtd.py:489-493
+  e.bias = w->b_final; e.act = VTD_ACT_NONE;
+  e.out = logits; e.ldo = 6; e.out_dtype = VTD_F32;
+  e.detections = dets;                                // transform_predictions, fused
+  return gemm_launch(HR, 6, m.kk(k), a, m.ka(k), w->w_final, m.kk(k), gdt, &e, st,
+                     2.0 * HR * (double)kv * 6);
+}
 }  // namespace
 
 }  // namespace vtd
@@ -479,15 +769,11 @@ int vtd_forward(const vtd_config* cfg, const vtd_weights* w, const float* images
                                        std::to_string(need) + " bytes)");
   hipStream_t st = static_cast<hipStream_t>(stream_);
   char* ws = static_cast<char*>(workspace);
+  // ns parts (1: the whole batch on the caller's stream).  No side stream for ns > 1 (a first
+  // call under capture): the parts run in order on `st`
   const int ns = split_count(cfg, d);
   SideStream* side = ns > 1 ? side_stream(st) : nullptr;
   const int n_stages = cfg->repeat_times + 2;
-  if (!side) {
-    bool partials = false;
-    if (ns == 1)
-      return forward_impl(cfg, w, images, logits, dets, ws, st, 0, n_stages, partials, 1, 1);
-    // no side stream (first call under capture): the halves run in order on `st`
-  }
   const size_t img = (size_t)cfg->image_h * cfg->image_w * cfg->channels;
   // one caller at a time per device from the fork record to the join wait (SideStream)
   std::unique_lock<std::mutex> side_lock;
@@ -499,40 +785,25 @@ int vtd_forward(const vtd_config* cfg, const vtd_weights* w, const float* images
   // phase otherwise (B = 96 / 128 / 256: 0 to -1.5 % with a stagger; profiles/r05_b64_split_ab.log)
   const int ks = knob(VTD_KNOB_STAGGER);
   const int part_tiles = (int)((d.rows / ns + 255) / 256);
-  const int stagger =
-      side ? std::min(ks >= 0 ? ks : (part_tiles <= 32 ? 1 : 0), n_stages) : 0;
+  const int stagger = side ? std::min(ks >= 0 ? ks : (part_tiles <= 32 ? 1 : 0), n_stages) : 0;
   auto fork = [&]() -> int {
     VTD_HIP(hipEventRecord(side->fork, st));
     for (int part = 1; part < ns; ++part) VTD_HIP(hipStreamWaitEvent(side->s[part - 1], side->fork, 0));
     return VTD_OK;
   };
   if (side && stagger == 0 && (rc = fork())) return rc;
-  struct Part {
-    vtd_config cfg;
-    const float* images;
-    float* logits;
-    float* dets;
-    char* ws;
-    hipStream_t st;
-    bool partials;
-  } parts[kMaxSplit];
+  Part parts[kMaxSplit];
   int64_t b0 = 0;
   size_t ws_off = 0;
   for (int part = 0; part < ns; ++part) {
-    Part& P = parts[part];
-    P.cfg = sub_config(cfg, part, ns);
-    vtd_dims dp;
-    rc = derive(&P.cfg, &dp);
-    if (rc) return rc;
-    P.st = side && part > 0 ? side->s[part - 1] : st;
+    const vtd_config pc = sub_config(cfg, part, ns);
     const size_t out_off = (size_t)b0 * VTD_MAX_DETECT * 6;
-    P.images = images + b0 * img;
-    P.logits = logits + out_off;
-    P.dets = dets ? dets + out_off : nullptr;
-    P.ws = ws + ws_off;
-    P.partials = false;
-    b0 += P.cfg.batch;
-    ws_off += make_plan(&P.cfg, dp, ns).total;
+    rc = parts[part].init(pc, w, images + b0 * img, logits + out_off,
+                          dets ? dets + out_off : nullptr, ws + ws_off,
+                          side && part > 0 ? side->s[part - 1] : st, ns, side ? ns : 1);
+    if (rc) return rc;
+    b0 += pc.batch;
+    ws_off += parts[part].P.total;
   }
   // Launches are interleaved part by part, one stage (encoder layer) at a time: issuing
   // all of one part's ~110 launches before the next part's first one left the second
@@ -542,12 +813,9 @@ int vtd_forward(const vtd_config* cfg, const vtd_weights* w, const float* images
     // issues stage k, so the other parts run exactly k stages behind
     if (side && stagger > 0 && t == stagger && (rc = fork())) return rc;
     for (int part = 0; part < ns; ++part) {
-      Part& P = parts[part];
       const int s = part == 0 ? t : t - stagger;
       if (s < 0 || s >= n_stages) continue;
-      rc = forward_impl(&P.cfg, w, P.images, P.logits, P.dets, P.ws, P.st, s, s + 1, P.partials,
-                        ns, side ? ns : 1);
-      if (rc) return rc;
+      if ((rc = parts[part].stage(s))) return rc;
     }
   }
   if (side) {                       // join: each side stream's record and the caller's wait
@@ -559,309 +827,6 @@ int vtd_forward(const vtd_config* cfg, const vtd_weights* w, const float* images
   return VTD_OK;
 }
 }  // extern "C"
-
-namespace vtd {
-namespace {
-int forward_impl(const vtd_config* cfg, const vtd_weights* w, const float* images,
-                 float* logits, float* dets, char* ws, hipStream_t st, int s_lo, int s_hi,
-                 bool& partials, int nparts, int nconc) {
-  vtd_dims d;
-  int rc = derive(cfg, &d);
-  if (rc) return rc;
-  const Plan P = make_plan(cfg, d, nparts);
-  const bool pad = nparts > 1 && split_pad();
-  const bool fp8 = cfg->dtype == VTD_FP8;
-  const int dt = act_dtype(cfg->dtype);
-  // VTD_BF16X3: every GEMM runs on split-bf16 operands (bf16 kernels over K' = 3 K_p, A rows
-  // stored [hi | lo], 2 K_p wide: ka), whose A operands the producers write directly (odt);
-  // qkv / attention / x stay f32
-  const bool x3 = cfg->dtype == VTD_BF16X3;
-  const int gdt = x3 ? VTD_BF16X3 : dt, odt = x3 ? VTD_BF16X3 : dt;
-  auto kk = [&](int k) { return opk(cfg->dtype, k); };
-  auto ka = [&](int k) { return opa(cfg->dtype, k); };
-  const int B = cfg->batch, N = d.tokens, D = d.d, Dp = d.d_p;
-  // R: the encoder's rows (the real batch x tokens, or whole 256-row tiles of a part: pad)
-  const int64_t R = gemm_rows(d, pad);
-  VTD_CHECK_ARG(R < (int64_t)1 << 31, "forward: batch*tokens too large");
-  const int M = (int)R;
-  void* patches = ws + P.patches;
-  const int rdt = resid_dtype(cfg->dtype);
-  float* stat = reinterpret_cast<float*>(ws + P.stat);
-  void* x = ws + P.x;
-  float* pstat = reinterpret_cast<float*>(ws + P.pstat);
-  const int nslot = Dp / 64;
-  // fold path: the GEMM writing x emits partial row statistics when it can (full tiles on
-  // the bf16 fast epilogues); the LayerNorm point then only finalizes them (`partials`)
-  static const bool partials_on = [] {       // VTD_LN_PARTIALS=0: row-statistics pass
-    const char* v = getenv("VTD_LN_PARTIALS");
-    return !v || atoi(v) != 0;
-  }();
-  auto emit_stats = [&](vtd_epilogue& e, bool next_fold) {
-    partials = false;
-    // centred per-block partials need every 64-column block full of valid columns
-    if (!next_fold || fp8 || dt != VTD_BF16 || !partials_on || D != Dp) return;
-    e.statout = pstat; e.stat_ld = (int)R;       // slot-major planes of R rows
-    partials = gemm_emits_stats(M, Dp, dt, &e);
-    if (!partials) { e.statout = nullptr; e.stat_ld = 0; }
-  };
-#ifndef VTD_DIAG
-#define VTD_DIAG 0
-#endif
-  // VTD_DIAG builds only (timing diagnostics, WRONG outputs): VTD_DIAG_NOFIN skips the
-  // LayerNorm finalize launches, VTD_DIAG_NOATTN the attention launches, VTD_DIAG_NOHEAD
-  // the detection head
-  // (VTD_DIAG_NOFIN=n: after the first n finalize launches, so the consumers keep applying
-  // the last real row statistics: activations stay realistic, MFMA power and clock with them)
-  static const int diag_nofin = VTD_DIAG && getenv("VTD_DIAG_NOFIN") ? atoi(getenv("VTD_DIAG_NOFIN")) : -1;
-  static std::atomic<int> diag_fin_count{0};
-  static const bool diag_noattn = VTD_DIAG && getenv("VTD_DIAG_NOATTN");
-  auto row_stats = [&]() -> int {
-    if (diag_nofin >= 0 && partials && diag_fin_count.fetch_add(1) >= diag_nofin) return VTD_OK;
-    return partials ? ln_stats_finalize_launch(pstat, R, nslot, D, 1e-3f, stat, st)
-                    : ln_stats_launch(x, rdt, R, D, Dp, 1e-3f, stat, st);
-  };
-  void* xb = ws + P.xb;
-  void* h = ws + P.h;
-  void* qkv = ws + P.qkv;
-  void* attn = ws + P.attn;
-  void* mlp[2] = {ws + P.mlp0, ws + P.mlp1};
-  void* u = ws + P.u;
-  void* head[2] = {ws + P.head0, ws + P.head1};
-  const int act = cfg->use_mish ? VTD_ACT_MISH : VTD_ACT_GELU_TANH;
-  const double fR = (double)d.rows;             // algorithmic FLOPs: the real rows
-  uint8_t* q8 = reinterpret_cast<uint8_t*>(ws + P.q8);
-  uint8_t* s8 = reinterpret_cast<uint8_t*>(ws + P.s8);
-  // encoder Dense layer (query/key/value, attention_output, MLP): bf16/f32 GEMM, or in
-  // VTD_FP8 mode MX-fp8 quantization of the bf16 A operand + the block-scaled MFMA GEMM
-  // against the MX-fp8 weights (W [Np][K8], S [K8/128][Np][4])
-  auto enc_gemm = [&](int Np, int K, const void* a, const void* W, const uint8_t* S,
-                      const vtd_epilogue* e, double flops) -> int {
-    if (!fp8) {
-      // few-tile, long-K layers (small batches) split K (enc_splitk_choice);
-      // not with partial statistics, which the split-K epilogue does not write
-      static const bool enc_split = [] {      // VTD_ENC_SPLITK=0: off (A/B)
-        const char* v = getenv("VTD_ENC_SPLITK");
-        return !v || atoi(v) != 0;
-      }();
-      const int ks = !enc_split || e->statout
-                         ? 1 : enc_splitk_choice(M, Np, kk(K), nparts, gdt, P.splitk_bytes);
-      if (ks > 1)
-        return gemm_splitk_launch(M, Np, kk(K), a, ka(K), W, kk(K), gdt, e,
-                                  reinterpret_cast<float*>(ws + P.splitk), ks, st, flops);
-      return gemm_launch(M, Np, kk(K), a, ka(K), W, kk(K), gdt, e, st, flops);
-    }
-    const int K8 = k8_of(K);
-    int r = quantize_mx8_launch(a, VTD_BF16, R, K, K, K8, q8, K8, s8, P.s8_rows, st);
-    if (r) return r;
-    return gemm_mx8_launch(M, Np, K8, q8, K8, s8, P.s8_rows, static_cast<const uint8_t*>(W), K8,
-                           S, Np, e, st, flops);
-  };
-  // VTD_FP8: the GEMM on an operand a producer already wrote as MX-fp8 (q, s)
-  uint8_t* q8b = reinterpret_cast<uint8_t*>(ws + P.q8b);
-  uint8_t* s8b = reinterpret_cast<uint8_t*>(ws + P.s8b);
-  auto mx_gemm = [&](int Np, int K, const uint8_t* qa, const uint8_t* sa, const void* W,
-                     const uint8_t* S, const vtd_epilogue* e, double flops) -> int {
-    const int K8 = k8_of(K);
-    return gemm_mx8_launch(M, Np, K8, qa, K8, sa, P.s8_rows, static_cast<const uint8_t*>(W), K8,
-                           S, Np, e, st, flops);
-  };
-  // VTD_FP8 LayerNorm straight into the MX-fp8 operand buffer q8 / s8
-  auto ln_mx8 = [&](const float* g, const float* b) -> int {
-    return layernorm_mx8_launch(x, rdt, R, D, Dp, g, b, 1e-3f, q8, k8_of(Dp), k8_of(Dp), s8,
-                                P.s8_rows, st);
-  };
-
-  const int n_stages = cfg->repeat_times + 2;
-  if (s_lo <= 0 && 0 < s_hi) {
-  // ---- ExtractImagePatches + flatten (vtd.py:271-280)
-  rc = patches_launch(images, B, cfg->image_h, cfg->image_w, cfg->channels,
-                      cfg->patch_size, patches, ka(d.patch_dim_p), odt, st);
-  if (rc) return rc;
-  if (R > d.rows) {                                   // pad rows: zero patches
-    const size_t row_bytes = (size_t)d.patch_dim_p * eop_of(cfg->dtype);
-    VTD_HIP(hipMemsetAsync(static_cast<char*>(patches) + (size_t)d.rows * row_bytes, 0,
-                           (size_t)(R - d.rows) * row_bytes, st));
-    // and the attention output's pad rows, which the attention never writes
-    const size_t attn_row = (size_t)d.inner_p * (x3 ? eop_of(cfg->dtype) : es_of(cfg->dtype));
-    VTD_HIP(hipMemsetAsync(static_cast<char*>(x3 ? ws + P.attn3 : attn) + (size_t)d.rows * attn_row,
-                           0, (size_t)(R - d.rows) * attn_row, st));
-  }
-  // ---- linear_projection + position embedding add (vtd.py:291-307)
-  {
-    vtd_epilogue e{};
-    e.bias = w->b_patch;
-    e.rowadd = w->pos_embedding; e.rowadd_period = N; e.rowadd_ncols = D;
-    e.act = VTD_ACT_NONE;
-    e.out = x; e.ldo = Dp; e.out_dtype = rdt;
-    emit_stats(e, cfg->repeat_times > 0 && w->layers[0].ln1_colsum);
-    rc = gemm_launch(M, Dp, kk(d.patch_dim_p), patches, ka(d.patch_dim_p), w->w_patch,
-                     kk(d.patch_dim_p), gdt, &e, st, 2.0 * fR * D * d.patch_dim);
-    if (rc) return rc;
-  }
-  }
-  const int q = cfg->mlp_quantities;
-  const float scale = 1.0f / std::sqrt((float)cfg->key_dim);
-  const int i_lo = std::max(s_lo - 1, 0), i_hi = std::min(s_hi - 1, cfg->repeat_times);
-  for (int i = i_lo; i < i_hi; ++i) {                  // vtd.py:350-412
-    const vtd_layer_weights& L = w->layers[i];
-    if ((fp8 || x3) && (L.ln1_colsum || L.ln2_colsum))
-      return fail(VTD_ERR_UNSUPPORTED, "forward: LayerNorm fold (ln*_colsum) is not supported in "
-                                       "the VTD_FP8 / VTD_BF16X3 modes");
-    // the folded GEMMs take the residual stream x itself as their A operand (read in dt)
-    if (rdt != dt && (L.ln1_colsum || L.ln2_colsum))
-      return fail(VTD_ERR_UNSUPPORTED, "forward: LayerNorm fold (ln*_colsum) needs the residual "
-                                       "stream in the compute dtype (unset VTD_RESID_F32)");
-    // LayerNorm 1: its own pass into h, or folded into the query/key/value GEMM
-    const void* a1 = h;
-    if (L.ln1_colsum) {
-      rc = row_stats();
-      a1 = x;
-    } else if (fp8) {
-      rc = ln_mx8(L.ln1_gamma, L.ln1_beta);       // LayerNorm + MX quantization, one pass
-    } else {
-      rc = layernorm_launch(x, rdt, R, D, Dp, L.ln1_gamma, L.ln1_beta, 1e-3f, h, ka(Dp), odt, st);
-    }
-    if (rc) return rc;
-    {
-      vtd_epilogue e{};
-      e.bias = L.b_qkv; e.act = VTD_ACT_NONE;
-      e.out = qkv; e.ldo = d.qkv_p; e.out_dtype = dt;
-      if (L.ln1_colsum) { e.lnstat = stat; e.colsum = L.ln1_colsum; }
-      const double fl = 2.0 * fR * D * 3.0 * cfg->num_heads * cfg->key_dim;
-      rc = fp8 ? mx_gemm(d.qkv_p, Dp, q8, s8, L.w_qkv, L.s_qkv, &e, fl)
-               : enc_gemm(d.qkv_p, Dp, a1, L.w_qkv, L.s_qkv, &e, fl);
-      if (rc) return rc;
-    }
-    // VTD_FP8 with whole MX K-steps: attention writes the output GEMM's MX-fp8 operand
-    const bool attn_mx8 = fp8 && d.inner_p % 128 == 0 && k8_of(d.inner_p) == d.inner_p;
-    const double attn_flops = 4.0 * B * cfg->num_heads * (double)N * N * cfg->key_dim;
-    rc = diag_noattn ? VTD_OK
-         : attn_mx8 ? attention_mx8_launch(qkv, B, N, cfg->num_heads, d.key_dim_p, d.qkv_p, scale,
-                                         q8, d.inner_p, s8, P.s8_rows, st, attn_flops)
-         : x3 ? attention_launch(qkv, B, N, cfg->num_heads, d.key_dim_p, d.qkv_p, scale,
-                                 ws + P.attn3, ka(d.inner_p), VTD_BF16X3, st, attn_flops, nconc)
-                  : attention_launch(qkv, B, N, cfg->num_heads, d.key_dim_p, d.qkv_p, scale,
-                                     attn, d.inner_p, dt, st, attn_flops, nconc);
-    if (rc) return rc;
-    // VTD_BF16X3: the attention wrote the attention_output GEMM's split-bf16 operand itself
-    const void* attn_op = x3 ? ws + P.attn3 : attn;
-    {
-      vtd_epilogue e{};
-      e.bias = L.b_out; e.act = VTD_ACT_NONE;
-      e.resid = x; e.ldr = Dp;
-      e.out = x; e.ldo = Dp; e.out_dtype = rdt;
-      emit_stats(e, L.ln2_colsum != nullptr);
-      const double fl = 2.0 * fR * cfg->num_heads * cfg->key_dim * D;
-      rc = attn_mx8 ? mx_gemm(Dp, d.inner_p, q8, s8, L.w_out, L.s_out, &e, fl)
-                    : enc_gemm(Dp, d.inner_p, attn_op, L.w_out, L.s_out, &e, fl);
-      if (rc) return rc;
-    }
-    const void* a = h;
-    // VTD_FP8: the current MLP operand as MX-fp8 (aq, as), written by its producer
-    const uint8_t* aq = nullptr;
-    const uint8_t* as = nullptr;
-    if (L.ln2_colsum) {
-      rc = row_stats();
-      a = x;
-    } else if (fp8) {
-      rc = ln_mx8(L.ln2_gamma, L.ln2_beta);
-      aq = q8; as = s8;
-    } else {
-      rc = layernorm_launch(x, rdt, R, D, Dp, L.ln2_gamma, L.ln2_beta, 1e-3f, h, ka(Dp), odt, st);
-    }
-    if (rc) return rc;
-    int k = Dp, kv = D;
-    for (int j = 0; j < q; ++j) {
-      const bool last = j == q - 1;
-      vtd_epilogue e{};
-      e.bias = L.b_mlp[j]; e.act = act;
-      if (j == 0 && L.ln2_colsum) { e.lnstat = stat; e.colsum = L.ln2_colsum; }
-      if (last) {
-        e.resid = x; e.ldr = Dp;
-        e.out = x; e.ldo = Dp; e.out_dtype = rdt;
-        if (i == cfg->repeat_times - 1 && dt == VTD_BF16 && rdt == VTD_F32) {
-          e.out2 = xb; e.ldo2 = Dp;           // bf16 copy of an f32 stream for the head
-        }
-        emit_stats(e, i + 1 < cfg->repeat_times && w->layers[i + 1].ln1_colsum);
-      } else {
-        e.out = mlp[j & 1]; e.ldo = ka(d.mlp_units_p[j]); e.out_dtype = odt;
-      }
-      // VTD_FP8: an inner MLP layer writes the next layer's MX-fp8 operand itself (into the
-      // operand buffer it is not reading) when every tile takes the fast epilogue
-      uint8_t* nq = nullptr;
-      uint8_t* ns = nullptr;
-      if (fp8 && !last) {
-        nq = aq == q8b ? q8 : q8b;        // (enc_gemm quantizes into q8)
-        ns = aq == q8b ? s8 : s8b;
-        vtd_epilogue ef = e;
-        ef.out = nq; ef.ldo = k8_of(d.mlp_units_p[j]); ef.out_dtype = VTD_FP8;
-        ef.scale_out = ns; ef.scale_rows = P.s8_rows;
-        if (gemm_mx8_emits_fp8(M, d.mlp_units_p[j], &ef)) e = ef;
-        else nq = ns = nullptr;
-      }
-      const double fl = 2.0 * fR * kv * d.mlp_units[j];
-      rc = aq ? mx_gemm(d.mlp_units_p[j], k, aq, as, L.w_mlp[j], L.s_mlp[j], &e, fl)
-              : enc_gemm(d.mlp_units_p[j], k, a, L.w_mlp[j], L.s_mlp[j], &e, fl);
-      if (rc) return rc;
-      a = mlp[j & 1];
-      aq = nq;
-      as = ns;
-      k = d.mlp_units_p[j];
-      kv = d.mlp_units[j];
-    }
-  }
-  if (!(s_lo <= n_stages - 1 && n_stages - 1 < s_hi)) return VTD_OK;
-  static const bool diag_nohead = VTD_DIAG && getenv("VTD_DIAG_NOHEAD");
-  if (diag_nohead) return VTD_OK;
-  // ---- mlp_head: Dense(17) + Reshape((17, -1)) as a scatter epilogue (vtd.py:454-463)
-  {
-    VTD_HIP(hipMemsetAsync(u, 0, (size_t)d.head_rows * d.tokens_p * eop_of(cfg->dtype), st));
-    vtd_epilogue e{};
-    e.bias = w->b_det; e.act = VTD_ACT_NONE;
-    e.out = u; e.ldo = ka(d.tokens_p); e.out_dtype = odt;
-    e.scatter_tokens = N;
-    const void* a = dt == rdt ? x : xb;
-    if (x3) {                        // the f32 stream x as the split-bf16 operand (h is free)
-      rc = split_bf16x3_launch(static_cast<const float*>(x), R, Dp, Dp, h, ka(Dp), 0, st);
-      if (rc) return rc;
-      a = h;
-    }
-    // the real rows only (the scatter addresses images by row)
-    rc = gemm_launch((int)d.rows, VTD_MAX_DETECT, kk(Dp), a, ka(Dp), w->w_det, kk(Dp), gdt, &e,
-                     st, 2.0 * fR * D * VTD_MAX_DETECT);
-    if (rc) return rc;
-  }
-  const int HR = (int)d.head_rows;
-  const void* a = u;
-  int k = d.tokens_p, kv = N;
-  for (int j = 0; j < d.n_head; ++j) {                // vtd.py:468-486
-    vtd_epilogue e{};
-    e.bias = w->b_head[j]; e.act = act;
-    e.out = head[j & 1]; e.ldo = ka(d.head_units_p[j]); e.out_dtype = odt;
-    const double fl = 2.0 * HR * (double)kv * d.head_units[j];
-    const int ks = gemm_splitk_choice(HR, d.head_units_p[j], kk(k), gdt, splitk_target(nparts));
-    rc = ks > 1 ? gemm_splitk_launch(HR, d.head_units_p[j], kk(k), a, ka(k), w->w_head[j], kk(k),
-                                     gdt, &e, reinterpret_cast<float*>(ws + P.splitk), ks, st, fl)
-                : gemm_launch(HR, d.head_units_p[j], kk(k), a, ka(k), w->w_head[j], kk(k), gdt,
-                              &e, st, fl);
-    if (rc) return rc;
-    a = head[j & 1];
-    k = d.head_units_p[j];
-    kv = d.head_units[j];
-  }
-  {                                                   // MLP_Head_no_Sigmoid vtd.py:489-493
-    vtd_epilogue e{};
-    e.bias = w->b_final; e.act = VTD_ACT_NONE;
-    e.out = logits; e.ldo = 6; e.out_dtype = VTD_F32;
-    e.detections = dets;                              // transform_predictions, fused
-    rc = gemm_launch(HR, 6, kk(k), a, ka(k), w->w_final, kk(k), gdt, &e, st,
-                     2.0 * HR * (double)kv * 6);
-    if (rc) return rc;
-  }
-  return VTD_OK;
-}
-}  // namespace
-}  // namespace vtd
 
 extern "C" {
 
