@@ -536,6 +536,100 @@ int vtd_ciou_grad(const float* label_bbox_dev, const float* pred_bbox_dev, int64
 int vtd_decode_grad(const float* logits_dev, const float* upstream_dev, int64_t n,
                     float* grad_dev, void* stream);
 
+/* ---------------------------------------------------------------- head backward - */
+/* Backward through the detection head (additions to ABI 17; nothing above changes): the
+ * weight and input gradients of mlp_head (vtd.py:417-495) given d loss / d logits
+ * (vtd_loss_grad), DESIGN.md "Head backward".  dtype below is VTD_BF16 or VTD_BF16X3; any
+ * other value returns VTD_ERR_UNSUPPORTED.
+ *
+ * vtd_gemm_wgrad: the weight gradient of a Dense layer, contracting over the ROW index of
+ * both operands:
+ *   dW[k][n] = sum_m X[m][k] * G[m][n]   (k < K, n < N; fp32, row-major [K][ldw]: the Keras
+ *              kernel layout),  db[n] = sum_m G[m][n]  (db_dev nullable).
+ * X, G in `dtype`, exactly as the forward's producers and vtd_act_grad store them:
+ *   VTD_BF16: bf16 rows, ldx >= K, ldg >= N, both % 8 == 0;
+ *   VTD_BF16X3: the split-bf16 A operand [hi | lo] with piece width ld / 2 (>= K resp. N),
+ *     ld % 16 == 0; dW = Xhi^T Ghi + Xlo^T Ghi + Xhi^T Glo, db from hi + lo.
+ * X_dev and G_dev 16-byte aligned; fp32 accumulation.  M is arbitrary: rows beyond M
+ * contribute zero (nothing is read past row M - 1).  Padding rule: K and N are the logical
+ * sizes; the kernel writes rows [0, K) of dW in full -- columns [N, ldw) of each as zero -- and
+ * nothing else.  A caller that wants a padded dW passes the padded K: the pad columns [K_real,
+ * K) of X are zero in every operand this library produces, so those rows come out zero.
+ * The grid is output tiles x `msplit` ranges of M (of ceil(M / 32) / msplit 32-row steps each):
+ * msplit == 1 writes dW directly; msplit > 1 writes fp32 partials to part_dev
+ * (part_bytes >= msplit * (K + 1) * N * 4; row K of each partial is its db) and one pass sums
+ * them in range order.  1 <= msplit <= min(ceil(M / 32), 256).  No atomics: the same inputs
+ * give the same bits on every run (the bits may differ between msplit values, as the order of
+ * the fp32 sum does).  vtd_gemm_wgrad_choice: the msplit vtd_head_backward uses.
+ * VTD_ERR_INVALID_ARG before any device call: a null X / G / dW (or part_dev with msplit > 1),
+ * non-positive sizes, the ld / alignment rules above, ldw < N, msplit out of range, part_bytes
+ * too small. */
+int vtd_gemm_wgrad(int M, int K, int N, const void* X_dev, int ldx, const void* G_dev, int ldg,
+                   int dtype, float* dW_dev, int ldw, float* db_dev, float* part_dev,
+                   size_t part_bytes, int msplit, void* stream);
+int vtd_gemm_wgrad_choice(int M, int K, int N, int dtype);
+
+/* a = act(z): z fp32 [rows][ldz] (first N columns) -> a_dev in `dtype` form [rows][lda]: bf16
+ * (lda >= N, lda % 8 == 0) or split-bf16 [hi | lo] (piece width lda / 2 >= N, lda % 16 == 0),
+ * 16-byte aligned; the columns [N, piece width) written as zero.  The activation is the GEMM
+ * epilogue's own device function (bit-identical); VTD_ACT_NONE converts only (for
+ * VTD_BF16X3 what vtd_split_bf16x3 role 0 writes).  The training forward of the head runs its
+ * Dense layers with VTD_ACT_NONE into fp32 z, keeps z, and applies this. */
+int vtd_act_forward(const float* z_dev, int64_t rows, int N, int ldz, int act, void* a_dev,
+                    int lda, int dtype, void* stream);
+/* gz = ga * act'(z): z [rows][ldz], ga [rows][ldga] fp32 -> gz_dev in `dtype` form as above --
+ * the A operand of the input-gradient GEMM and the G operand of vtd_gemm_wgrad.  The
+ * derivatives use the forward's exp2 / rcp formulation (GELU-tanh through s = 1 / (1 + 2^(x (c0
+ * + c1 x^2))), Mish through n = e (e + 2)); finite for every finite z, exactly 1 for Mish
+ * where the forward returns x (z > 20); within 1e-5 of the fp64 derivative. */
+int vtd_act_grad(const float* z_dev, int ldz, const float* ga_dev, int ldga, int64_t rows, int N,
+                 int act, void* gz_dev, int ldgz, int dtype, void* stream);
+/* Inverse of the Reshape scatter epilogue (vtd_epilogue.scatter_tokens, vtd.py:461-463):
+ * dU fp32 [B * 17][ldu] (ldu >= T) -> dT [B * T][ldt] in `dtype` form (piece width >= 17):
+ * element (b T + t, n < 17) = dU[b * 17 + f / T][f % T], f = t * 17 + n; the columns from 17
+ * to the piece width zero. */
+int vtd_head_unscatter(const float* dU_dev, int B, int T, int ldu, void* dT_dev, int ldt,
+                       int dtype, void* stream);
+
+/* Stages 0 .. L of vtd_forward (patches, projection, the encoder layers: the same parts, streams
+ * and workspace, vtd_workspace_bytes) and then, instead of the head, the residual stream after
+ * the last layer -- Keras layer `encoded_images` -- as fp32 [B * N][d], unpadded.  (VTD_BF16 /
+ * VTD_FP8: the stream is held in bf16; these are its values.) */
+int vtd_forward_encoded(const vtd_config* cfg, const vtd_weights* w, const float* images_dev,
+                        float* encoded_dev, void* workspace_dev, size_t workspace_bytes,
+                        void* stream);
+
+/* The head's weights, fp32 device arrays in the Keras layout, unpadded: kernels [K][N]
+ * row-major, biases [N].  w_det / b_det: `dense` [d][17]; w_head[j] / b_head[j], j <
+ * vtd_dims.n_head: `dense_{j+1}` [tokens or head_units[j-1]][head_units[j]]; w_final / b_final:
+ * `MLP_Head_no_Sigmoid` [head_units[n_head-1]][6].  vtd_head_grads: outputs of the same shapes,
+ * and d_encoded fp32 [B * N][d] = d loss / d encoded_images (nullable: not computed). */
+typedef struct vtd_head_params {
+  const float* w_det; const float* b_det;
+  const float* w_head[VTD_MAX_HEAD]; const float* b_head[VTD_MAX_HEAD];
+  const float* w_final; const float* b_final;
+} vtd_head_params;
+typedef struct vtd_head_grads {
+  float* w_det; float* b_det;
+  float* w_head[VTD_MAX_HEAD]; float* b_head[VTD_MAX_HEAD];
+  float* w_final; float* b_final;
+  float* d_encoded;
+} vtd_head_grads;
+/* One call: the training forward of the head from encoded_dev (fp32 [B * N][d], as
+ * vtd_forward_encoded writes it) keeping every pre-activation z and activation, then the
+ * backward from dlogits_dev (fp32 [B][17][6]) into *g.  logits_dev (nullable): the training
+ * forward's logits.  dlogits_dev NULL (logits_dev then required, g ignored): the training
+ * forward alone, for the logits the loss gradient is taken at.  Weights change every step, so the call converts what it needs into the
+ * workspace itself (W^T for the forward GEMMs, the [K][N] form for the input-gradient GEMMs).
+ * cfg->dtype VTD_BF16X3 or VTD_BF16 (else VTD_ERR_UNSUPPORTED); every Dense product runs in
+ * that mode's operands with fp32 accumulation.  Asynchronous on `stream` (one part, no side
+ * streams), no allocation, no host synchronisation, bit-identical from run to run.
+ * ws_bytes >= vtd_head_backward_workspace_bytes (else VTD_ERR_WORKSPACE). */
+int vtd_head_backward_workspace_bytes(const vtd_config* cfg, size_t* bytes);
+int vtd_head_backward(const vtd_config* cfg, const vtd_head_params* w, const float* encoded_dev,
+                      const float* dlogits_dev, float* logits_dev, const vtd_head_grads* g,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* Optional per-kernel timing of vtd_forward (hipEvents on `stream`, recorded around
  * every launch while enabled).  vtd_profile_read returns per-class totals in ms
  * summed over the forwards since the last reset; classes: 0 gemm, 1 attention,

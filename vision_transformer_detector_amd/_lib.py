@@ -89,6 +89,17 @@ class VtdLossParams(ctypes.Structure):
                 ("from_logits", c_int)]
 
 
+class VtdHeadParams(ctypes.Structure):
+    """vtd_head_params (fp32 Keras-layout weights) and, with the extra d_encoded field,
+    vtd_head_grads (VtdHeadGrads below)."""
+    _fields_ = [("w_det", c_void_p), ("b_det", c_void_p), ("w_head", c_void_p * MAX_HEAD),
+                ("b_head", c_void_p * MAX_HEAD), ("w_final", c_void_p), ("b_final", c_void_p)]
+
+
+class VtdHeadGrads(ctypes.Structure):
+    _fields_ = VtdHeadParams._fields_ + [("d_encoded", c_void_p)]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "vtd_abi_version": (c_int, []),
@@ -163,6 +174,22 @@ SIGNATURES = {
     "vtd_ciou_grad": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
                               c_void_p]),
     "vtd_decode_grad": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "vtd_gemm_wgrad": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                               c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "vtd_gemm_wgrad_choice": (c_int, [c_int, c_int, c_int, c_int]),
+    "vtd_act_forward": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                c_void_p]),
+    "vtd_act_grad": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_void_p,
+                             c_int, c_int, c_void_p]),
+    "vtd_head_unscatter": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                   c_void_p]),
+    "vtd_forward_encoded": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdWeights),
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vtd_head_backward_workspace_bytes": (c_int, [ctypes.POINTER(VtdConfig),
+                                                  ctypes.POINTER(c_size_t)]),
+    "vtd_head_backward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdHeadParams),
+                                  c_void_p, c_void_p, c_void_p, ctypes.POINTER(VtdHeadGrads),
+                                  c_void_p, c_size_t, c_void_p]),
     "vtd_forward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdWeights), c_void_p,
                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vtd_set_knob": (c_int, [c_int, c_int]),

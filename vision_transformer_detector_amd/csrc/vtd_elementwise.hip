@@ -1001,9 +1001,258 @@ int decode_launch(const float* logits, int64_t n, float* dets, hipStream_t st) {
   return VTD_OK;
 }
 
+// ------------------------------------------------------------------ head backward pieces
+namespace {
+// d act_mish / dx in the forward's formulation (vtd_common.h): with e = e^x, n = e (e + 2),
+// r = 1 / (n + 2): tanh(softplus(x)) = n r, 1 - tanh^2 = 4 (e + 1)^2 r^2, sigmoid = e / (e + 1),
+// so d/dx = n r + x * 4 e (e + 1) r^2.  Exactly 1 where the forward returns x (x > 20, where e
+// would later overflow); e -> 0 for x << 0 gives x * 0: finite for every finite x.
+__device__ __forceinline__ float act_mish_grad(float x) {
+  const float e = __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
+  const float n = e * (e + 2.f);
+  const float r = __builtin_amdgcn_rcpf(n + 2.f);
+  const float d = n * r + x * (4.f * e * (e + 1.f)) * (r * r);
+  return x > 20.f ? 1.f : d;
+}
+// d act_gelu / dx: with w = x (c0 + c1 x^2), E = 2^w, s = 1 / (1 + E) (the forward's x * s):
+// d/dx = s - ln2 x (c0 + 3 c1 x^2) s (E s).  E s = 1 - s is taken as 1 - s where E > 1 (no
+// cancellation there, and E = inf stays finite).  |x| >= 12 saturates in fp32 (s is exactly 1
+// or 0 and the second term 0), so x is clamped to [-12, 12]: finite for every finite x.
+__device__ __forceinline__ float act_gelu_grad(float x) {
+  constexpr float c0 = -2.f * 0.7978845608028654f * 1.4426950408889634f;
+  constexpr float c1 = c0 * 0.044715f;
+  x = fminf(fmaxf(x, -12.f), 12.f);
+  const float x2 = x * x;
+  const float E = __builtin_amdgcn_exp2f(x * __builtin_fmaf(c1, x2, c0));
+  const float s = __builtin_amdgcn_rcpf(1.f + E);
+  const float es = E > 1.f ? 1.f - s : E * s;
+  return s - 0.6931471805599453f * x * __builtin_fmaf(3.f * c1, x2, c0) * s * es;
+}
+
+// 8 fp32 values -> the `dtype` form at columns c0 .. c0 + 7 of a row: bf16, or split-bf16
+// [hi | lo] with P-wide pieces (the same conversions as split_bf16x3_kernel)
+__device__ __forceinline__ void store_op8(const float (&v)[8], bf16_t* yr, int c0, int P, bool x3) {
+  uint4 hi, lo;
+  hi.x = pack_bf16x2(v[0], v[1]); lo.x = pack_lo_bf16x2(v[0], v[1], hi.x);
+  hi.y = pack_bf16x2(v[2], v[3]); lo.y = pack_lo_bf16x2(v[2], v[3], hi.y);
+  hi.z = pack_bf16x2(v[4], v[5]); lo.z = pack_lo_bf16x2(v[4], v[5], hi.z);
+  hi.w = pack_bf16x2(v[6], v[7]); lo.w = pack_lo_bf16x2(v[6], v[7], hi.w);
+  *reinterpret_cast<uint4*>(yr + c0) = hi;
+  if (x3) *reinterpret_cast<uint4*>(yr + P + c0) = lo;
+}
+
+// MODE 0: y = act(z); MODE 1: y = ga * act'(z).  One thread per 8 columns of a row of the
+// P-wide output piece; columns [N, P) zero.
+template <int MODE>
+__global__ __launch_bounds__(256) void act_op_kernel(const float* __restrict__ z, int ldz,
+                                                     const float* __restrict__ ga, int ldga,
+                                                     int64_t rows, int N, int act,
+                                                     bf16_t* __restrict__ y, int ldy, int P,
+                                                     int x3) {
+  const int chunks = P / 8;
+  const int64_t total = rows * chunks;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = g / chunks;
+    const int c0 = (int)(g - m * chunks) * 8;
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int c = c0 + i;
+      float r = 0.f;
+      if (c < N) {
+        const float x = z[m * ldz + c];
+        if (MODE == 0) {
+          r = apply_act(act, x);
+        } else {
+          const float d = act == VTD_ACT_MISH ? act_mish_grad(x)
+                          : act == VTD_ACT_GELU_TANH ? act_gelu_grad(x) : 1.f;
+          r = ga[m * ldga + c] * d;
+        }
+      }
+      v[i] = r;
+    }
+    store_op8(v, y + m * ldy, c0, P, x3 != 0);
+  }
+}
+
+// inverse of the head's Reshape scatter epilogue: dT[b T + t][n] = dU[b 17 + f / T][f % T],
+// f = 17 t + n, n < 17; columns [17, P) zero
+__global__ __launch_bounds__(256) void head_unscatter_kernel(const float* __restrict__ dU, int ldu,
+                                                             int B, int T,
+                                                             bf16_t* __restrict__ y, int ldy,
+                                                             int P, int x3) {
+  const int chunks = P / 8;
+  const int64_t total = (int64_t)B * T * chunks;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = g / chunks;
+    const int c0 = (int)(g - m * chunks) * 8;
+    const int b = (int)(m / T), t = (int)(m - (int64_t)b * T);
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int n = c0 + i;
+      float r = 0.f;
+      if (n < VTD_MAX_DETECT) {
+        const int f = t * VTD_MAX_DETECT + n;
+        r = dU[((int64_t)b * VTD_MAX_DETECT + f / T) * ldu + f % T];
+      }
+      v[i] = r;
+    }
+    store_op8(v, y + m * ldy, c0, P, x3 != 0);
+  }
+}
+
+int op_form(const char* what, const void* y, int ldy, int dtype, int N, int* P) {
+  if (dtype != VTD_BF16 && dtype != VTD_BF16X3)
+    return fail(VTD_ERR_UNSUPPORTED, std::string(what) + ": dtype must be VTD_BF16 or VTD_BF16X3");
+  const bool x3 = dtype == VTD_BF16X3;
+  VTD_CHECK_ARG(ldy > 0 && ldy % (x3 ? 16 : 8) == 0,
+                std::string(what) + ": output ld must be a multiple of 8 (VTD_BF16X3: 16)");
+  *P = x3 ? ldy / 2 : ldy;
+  VTD_CHECK_ARG(*P >= N, std::string(what) + ": output piece narrower than N");
+  VTD_CHECK_ARG(reinterpret_cast<uintptr_t>(y) % 16 == 0,
+                std::string(what) + ": output must be 16-byte aligned");
+  return VTD_OK;
+}
+int op_grid(int64_t total) { return (int)std::min<int64_t>((total + 255) / 256, 16384); }
+
+// Keras kernel src fp32 [K][N] -> W^T in operand form dst [Np][ld]: bf16 (ld = Kp) or the
+// split-bf16 B operand [hi | hi | lo] (ld = 3 Kp), dst[n][k] = src[k][n], every pad row and
+// column written as zero.  32 x 32 tiles through LDS: coalesced reads along n, writes along k.
+__global__ __launch_bounds__(256) void transpose_op_kernel(const float* __restrict__ src, int K,
+                                                           int N, bf16_t* __restrict__ dst,
+                                                           int Kp, int Np, int x3, int tiles_k) {
+  __shared__ float tile[32][33];
+  const int k0 = (blockIdx.x % tiles_k) * 32, n0 = (blockIdx.x / tiles_k) * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < 32; r += 8) {
+    const int k = k0 + r, n = n0 + tx;
+    tile[r][tx] = k < K && n < N ? src[(int64_t)k * N + n] : 0.f;
+  }
+  __syncthreads();
+  const int ld = x3 ? 3 * Kp : Kp;
+  for (int r = ty; r < 32; r += 8) {
+    const int n = n0 + r, k = k0 + tx;
+    if (n < Np && k < Kp) {
+      const float v = tile[tx][r];
+      const bf16_t h = f32_to_bf16(v);
+      bf16_t* o = dst + (int64_t)n * ld + k;
+      o[0] = h;
+      if (x3) {
+        o[Kp] = h;
+        o[2 * Kp] = lo_bf16(v, h);
+      }
+    }
+  }
+}
+
+// x [rows][ldx] (fp32 or bf16) -> y fp32 [rows][D]: the first D columns
+template <typename T>
+__global__ __launch_bounds__(256) void unpad_f32_kernel(const T* __restrict__ x, int ldx,
+                                                        int64_t rows, int D,
+                                                        float* __restrict__ y) {
+  const int64_t total = rows * D;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = g / D;
+    y[g] = DT<T>::load(x + m * ldx + (g - m * D));
+  }
+}
+}  // namespace
+
+int transpose_op_launch(const float* src, int K, int N, void* dst, int Kp, int Np, int dtype,
+                        hipStream_t st) {
+  VTD_CHECK_ARG(src && dst && K > 0 && N > 0 && Kp >= K && Np >= N, "transpose_op: bad arguments");
+  VTD_CHECK_ARG(dtype == VTD_BF16 || dtype == VTD_BF16X3, "transpose_op: bf16 or split-bf16");
+  const int64_t tiles_k = (Kp + 31) / 32, tiles_n = (Np + 31) / 32;
+  VTD_CHECK_ARG(tiles_k * tiles_n < (int64_t)1 << 31, "transpose_op: matrix too large");
+  ProfScope ps(st, PROF_OTHER, 0.0);
+  hipLaunchKernelGGL(transpose_op_kernel, dim3((unsigned)(tiles_k * tiles_n)), dim3(256), 0, st,
+                     src, K, N, static_cast<bf16_t*>(dst), Kp, Np, dtype == VTD_BF16X3 ? 1 : 0,
+                     (int)tiles_k);
+  VTD_LAUNCH_CHECK("transpose_op");
+  return VTD_OK;
+}
+
+int unpad_f32_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx, float* y,
+                     hipStream_t st) {
+  VTD_CHECK_ARG(x && y && rows > 0 && D > 0 && ldx >= D, "unpad: bad arguments");
+  ProfScope ps(st, PROF_OTHER, 0.0);
+  if (x_dtype == VTD_BF16)
+    hipLaunchKernelGGL(unpad_f32_kernel<bf16_t>, dim3(op_grid(rows * D)), dim3(256), 0, st,
+                       static_cast<const bf16_t*>(x), ldx, rows, D, y);
+  else
+    hipLaunchKernelGGL(unpad_f32_kernel<float>, dim3(op_grid(rows * D)), dim3(256), 0, st,
+                       static_cast<const float*>(x), ldx, rows, D, y);
+  VTD_LAUNCH_CHECK("unpad");
+  return VTD_OK;
+}
+
+int act_forward_launch(const float* z, int64_t rows, int N, int ldz, int act, void* y, int ldy,
+                       int dtype, hipStream_t st) {
+  VTD_CHECK_ARG(z && y && rows > 0 && N > 0 && ldz >= N, "act_forward: bad arguments");
+  VTD_CHECK_ARG(act >= VTD_ACT_NONE && act <= VTD_ACT_MISH, "act_forward: unknown activation");
+  int P;
+  if (int rc = op_form("act_forward", y, ldy, dtype, N, &P)) return rc;
+  ProfScope ps(st, PROF_OTHER, 0.0);
+  hipLaunchKernelGGL(act_op_kernel<0>, dim3(op_grid(rows * (P / 8))), dim3(256), 0, st, z, ldz,
+                     (const float*)nullptr, 0, rows, N, act, static_cast<bf16_t*>(y), ldy, P,
+                     dtype == VTD_BF16X3 ? 1 : 0);
+  VTD_LAUNCH_CHECK("act_forward");
+  return VTD_OK;
+}
+
+int act_grad_launch(const float* z, int ldz, const float* ga, int ldga, int64_t rows, int N,
+                    int act, void* y, int ldy, int dtype, hipStream_t st) {
+  VTD_CHECK_ARG(z && ga && y && rows > 0 && N > 0 && ldz >= N && ldga >= N,
+                "act_grad: bad arguments");
+  VTD_CHECK_ARG(act >= VTD_ACT_NONE && act <= VTD_ACT_MISH, "act_grad: unknown activation");
+  int P;
+  if (int rc = op_form("act_grad", y, ldy, dtype, N, &P)) return rc;
+  ProfScope ps(st, PROF_OTHER, 0.0);
+  hipLaunchKernelGGL(act_op_kernel<1>, dim3(op_grid(rows * (P / 8))), dim3(256), 0, st, z, ldz,
+                     ga, ldga, rows, N, act, static_cast<bf16_t*>(y), ldy, P,
+                     dtype == VTD_BF16X3 ? 1 : 0);
+  VTD_LAUNCH_CHECK("act_grad");
+  return VTD_OK;
+}
+
+int head_unscatter_launch(const float* dU, int B, int T, int ldu, void* y, int ldy, int dtype,
+                          hipStream_t st) {
+  VTD_CHECK_ARG(dU && y && B > 0 && T > 0 && ldu >= T, "head_unscatter: bad arguments");
+  int P;
+  if (int rc = op_form("head_unscatter", y, ldy, dtype, VTD_MAX_DETECT, &P)) return rc;
+  ProfScope ps(st, PROF_OTHER, 0.0);
+  hipLaunchKernelGGL(head_unscatter_kernel, dim3(op_grid((int64_t)B * T * (P / 8))), dim3(256), 0,
+                     st, dU, ldu, B, T, static_cast<bf16_t*>(y), ldy, P,
+                     dtype == VTD_BF16X3 ? 1 : 0);
+  VTD_LAUNCH_CHECK("head_unscatter");
+  return VTD_OK;
+}
+
 }  // namespace vtd
 
 extern "C" {
+
+int vtd_act_forward(const float* z_dev, int64_t rows, int N, int ldz, int act, void* a_dev,
+                    int lda, int dtype, void* stream) {
+  return vtd::act_forward_launch(z_dev, rows, N, ldz, act, a_dev, lda, dtype,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int vtd_act_grad(const float* z_dev, int ldz, const float* ga_dev, int ldga, int64_t rows, int N,
+                 int act, void* gz_dev, int ldgz, int dtype, void* stream) {
+  return vtd::act_grad_launch(z_dev, ldz, ga_dev, ldga, rows, N, act, gz_dev, ldgz, dtype,
+                              static_cast<hipStream_t>(stream));
+}
+
+int vtd_head_unscatter(const float* dU_dev, int B, int T, int ldu, void* dT_dev, int ldt,
+                       int dtype, void* stream) {
+  return vtd::head_unscatter_launch(dU_dev, B, T, ldu, dT_dev, ldt, dtype,
+                                    static_cast<hipStream_t>(stream));
+}
 
 int vtd_layernorm(const void* x_dev, int x_dtype, int64_t rows, int D, int ldx,
                   const float* gamma_dev, const float* beta_dev, float eps, void* y_dev, int ldy,

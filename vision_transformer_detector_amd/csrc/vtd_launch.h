@@ -29,6 +29,12 @@ void gemm_mx8_x4_launch(int M, int N, int K, const uint8_t* A, int lda, const ui
                         int64_t sb_rows, const vtd_epilogue* epi, int ngw, hipStream_t stream);
 #endif
 
+// ----------------------------------------------------------------- vtd_gemm_wgrad.hip
+int gemm_wgrad_choice(int M, int K, int N, int dtype);
+int gemm_wgrad_launch(int M, int K, int N, const void* X, int ldx, const void* G, int ldg,
+                      int dtype, float* dW, int ldw, float* db, float* part, size_t part_bytes,
+                      int msplit, hipStream_t stream);
+
 // ----------------------------------------------------------------- vtd_attention.hip
 int attention_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
                      float scale, void* out, int ldo, int dtype, hipStream_t stream,
@@ -51,6 +57,16 @@ int patches_launch(const float* img, int B, int H, int W, int C, int p, void* ou
                    int dtype, hipStream_t st);
 int split_bf16x3_launch(const float* x, int64_t rows, int K, int ldx, void* y, int ldy, int role,
                         hipStream_t st);
+int unpad_f32_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx, float* y,
+                     hipStream_t st);
+int transpose_op_launch(const float* src, int K, int N, void* dst, int Kp, int Np, int dtype,
+                        hipStream_t st);
+int act_forward_launch(const float* z, int64_t rows, int N, int ldz, int act, void* y, int ldy,
+                       int dtype, hipStream_t st);
+int act_grad_launch(const float* z, int ldz, const float* ga, int ldga, int64_t rows, int N,
+                    int act, void* y, int ldy, int dtype, hipStream_t st);
+int head_unscatter_launch(const float* dU, int B, int T, int ldu, void* y, int ldy, int dtype,
+                          hipStream_t st);
 
 // ----------------------------------------------------------------- vtd_mx8.hip
 int quantize_mx8_launch(const void* x, int x_dtype, int64_t rows, int K, int ldx, int Kq,

@@ -451,6 +451,7 @@ struct Part {
   const vtd_weights* w;
   const float* images;
   float *logits, *dets;
+  float* encoded = nullptr;  // vtd_forward_encoded: the last stage writes x here, no head
   hipStream_t st;
   int nparts, nconc;
   int64_t R; int M;          // the encoder's rows (gemm_rows: whole 256-row tiles of a part)
@@ -463,7 +464,10 @@ struct Part {
 
   int init(const vtd_config& c, const vtd_weights* w, const float* images, float* logits,
            float* dets, char* ws, hipStream_t st, int nparts, int nconc);
-  int stage(int s) { return s == 0 ? embed() : s <= cfg.repeat_times ? layer(s - 1) : head(); }
+  int stage(int s) {
+    return s == 0 ? embed() : s <= cfg.repeat_times ? layer(s - 1) : encoded ? emit_encoded() : head();
+  }
+  int emit_encoded();
   int embed();
   int layer(int i);                       // attention block, then mlp_stack(i)
   int mlp_stack(int i);
@@ -678,6 +682,12 @@ int Part::mlp_stack(int i) {
   return VTD_OK;
 }
 
+// Keras layer `encoded_images`: the residual stream after the last encoder layer, the real rows
+// and columns only, as fp32
+int Part::emit_encoded() {
+  return unpad_f32_launch(x, m.resid, d.rows, d.d, d.d_p, encoded, st);
+}
+
 int Part::head() {
   if (switches().diag_nohead) return VTD_OK;
   const int N = d.tokens, D = d.d, Dp = d.d_p, HR = (int)d.head_rows, gdt = m.op;
@@ -755,13 +765,17 @@ int vtd_workspace_bytes(const vtd_config* cfg, size_t* bytes) {
   return *bytes ? VTD_OK : fail(VTD_ERR_INVALID_ARG, "workspace: bad split config");
 }
 
-int vtd_forward(const vtd_config* cfg, const vtd_weights* w, const float* images,
-                float* logits, float* dets, void* workspace, size_t workspace_bytes,
-                void* stream_) {
+}  // extern "C"
+
+// The driver of vtd_forward (encoded == NULL: stages 0 .. L + 1, the head writes logits / dets)
+// and of vtd_forward_encoded (stages 0 .. L, then the residual stream into `encoded`).
+static int run_forward(const vtd_config* cfg, const vtd_weights* w, const float* images,
+                       float* logits, float* dets, float* encoded, void* workspace,
+                       size_t workspace_bytes, void* stream_) {
   vtd_dims d;
   int rc = derive(cfg, &d);
   if (rc) return rc;
-  VTD_CHECK_ARG(w && images && logits && workspace, "forward: null pointer");
+  VTD_CHECK_ARG(w && images && (logits || encoded) && workspace, "forward: null pointer");
   VTD_CHECK_ARG(w->layers, "forward: weights.layers is null");
   const size_t need = split_workspace(cfg, d);
   if (workspace_bytes < need)
@@ -802,6 +816,7 @@ int vtd_forward(const vtd_config* cfg, const vtd_weights* w, const float* images
                           dets ? dets + out_off : nullptr, ws + ws_off,
                           side && part > 0 ? side->s[part - 1] : st, ns, side ? ns : 1);
     if (rc) return rc;
+    if (encoded) parts[part].encoded = encoded + (size_t)b0 * d.tokens * d.d;
     b0 += pc.batch;
     ws_off += parts[part].P.total;
   }
@@ -826,6 +841,266 @@ int vtd_forward(const vtd_config* cfg, const vtd_weights* w, const float* images
   }
   return VTD_OK;
 }
+
+
+// ------------------------------------------------------------------ head backward
+// Workspace of vtd_head_backward: buffers in use order, 256-B aligned.  The converted weights
+// (wt: W^T for a forward GEMM, wkn: the Keras [K][N] form for an input-gradient GEMM) are one
+// buffer each, sized for the largest layer and reused layer by
+// layer -- the call runs on one stream, so the order of the launches is the order of use.
+namespace {
+struct HeadPlan {
+  size_t a_enc, u, z[VTD_MAX_HEAD], a[VTD_MAX_HEAD], logits, gf, gz, da[2], dt, wt, wkn, bias,
+      part, part_bytes, total;
+  int fwd_ks[VTD_MAX_HEAD];       // split-K of the forward GEMM of head layer j
+  int bwd_ks[VTD_MAX_HEAD + 1];   // of the input-gradient GEMM of layer j (n_head: the final one)
+  int wg_ms[VTD_MAX_HEAD + 2];    // msplit of the weight gradient: j, n_head = final, n_head + 1 = dense
+};
+HeadPlan head_plan(const vtd_dims& d, const Mode& m) {
+  HeadPlan p{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    size_t o = off;
+    off += (bytes + 255) / 256 * 256;
+    return o;
+  };
+  const size_t R = (size_t)d.rows, HR = (size_t)d.head_rows, eop = m.eop;
+  const int nh = d.n_head, op = m.op;
+  size_t wmax = (size_t)64 * d.d_p, umax = std::max(d.tokens_p, 64), part = 0;
+  p.a_enc = take(R * d.d_p * eop);
+  p.u = take(HR * d.tokens_p * eop);
+  for (int j = 0, k = d.tokens_p, kv = d.tokens; j < nh; k = d.head_units_p[j], kv = d.head_units[j], ++j) {
+    const int up = d.head_units_p[j];
+    p.z[j] = take(HR * up * 4);
+    p.a[j] = take(HR * up * eop);
+    wmax = std::max(wmax, (size_t)up * k);
+    umax = std::max<size_t>(umax, up);
+    p.fwd_ks[j] = gemm_splitk_choice((int)HR, up, m.kk(k), op);
+    p.bwd_ks[j] = gemm_splitk_choice((int)HR, k, m.kk(up), op);
+    p.wg_ms[j] = gemm_wgrad_choice((int)HR, kv, d.head_units[j], op);
+    part = std::max(part, (size_t)p.fwd_ks[j] * HR * up * 4);
+    part = std::max(part, (size_t)p.bwd_ks[j] * HR * k * 4);
+    if (p.wg_ms[j] > 1) part = std::max(part, (size_t)p.wg_ms[j] * (kv + 1) * d.head_units[j] * 4);
+  }
+  const int kl = nh ? d.head_units_p[nh - 1] : d.tokens_p, klv = nh ? d.head_units[nh - 1] : d.tokens;
+  wmax = std::max(wmax, (size_t)64 * kl);
+  p.bwd_ks[nh] = gemm_splitk_choice((int)HR, kl, m.kk(64), op);
+  p.wg_ms[nh] = gemm_wgrad_choice((int)HR, klv, 6, op);
+  p.wg_ms[nh + 1] = gemm_wgrad_choice((int)R, d.d, VTD_MAX_DETECT, op);
+  part = std::max(part, (size_t)p.bwd_ks[nh] * HR * kl * 4);
+  if (p.wg_ms[nh] > 1) part = std::max(part, (size_t)p.wg_ms[nh] * (klv + 1) * 6 * 4);
+  if (p.wg_ms[nh + 1] > 1)
+    part = std::max(part, (size_t)p.wg_ms[nh + 1] * (d.d + 1) * VTD_MAX_DETECT * 4);
+  p.logits = take(HR * 6 * 4);
+  p.gf = take(HR * 64 * eop);
+  p.gz = take(HR * umax * eop);
+  p.da[0] = take(HR * umax * 4);
+  p.da[1] = take(HR * umax * 4);
+  p.dt = take(R * 64 * eop);
+  p.wt = take(wmax * (m.x3 ? 6 : 2));
+  p.wkn = take(wmax * (m.x3 ? 6 : 2));
+  p.bias = take(umax * 4);
+  p.part_bytes = part;
+  p.part = take(part);
+  p.total = off;
+  return p;
+}
+int head_mode(const vtd_config* cfg, vtd_dims* d, const char* what) {
+  if (int rc = derive(cfg, d)) return rc;
+  if (cfg->dtype != VTD_BF16X3 && cfg->dtype != VTD_BF16)
+    return fail(VTD_ERR_UNSUPPORTED, std::string(what) + ": cfg->dtype must be VTD_BF16X3 or "
+                                     "VTD_BF16 (VTD_F32 and VTD_FP8 have no backward)");
+  VTD_CHECK_ARG(d->rows < (int64_t)1 << 31, std::string(what) + ": batch*tokens too large");
+  return VTD_OK;
+}
+}  // namespace
+
+static int head_backward(const vtd_config* cfg, const vtd_head_params* w, const float* encoded,
+                         const float* dlogits, float* logits_out, const vtd_head_grads* g,
+                         void* ws_, size_t ws_bytes, void* stream_) {
+  vtd_dims d;
+  if (int rc = head_mode(cfg, &d, "head_backward")) return rc;
+  VTD_CHECK_ARG(w && encoded && ws_ && (dlogits ? g != nullptr : logits_out != nullptr),
+                "head_backward: null pointer");
+  const int nh = d.n_head;
+  VTD_CHECK_ARG(w->w_det && w->b_det && w->w_final && w->b_final,
+                "head_backward: null weight pointer");
+  for (int j = 0; j < nh; ++j)
+    VTD_CHECK_ARG(w->w_head[j] && w->b_head[j], "head_backward: null weight pointer");
+  if (dlogits) {
+    VTD_CHECK_ARG(g->w_det && g->b_det && g->w_final && g->b_final,
+                  "head_backward: null gradient pointer");
+    for (int j = 0; j < nh; ++j)
+      VTD_CHECK_ARG(g->w_head[j] && g->b_head[j], "head_backward: null gradient pointer");
+  }
+  const Mode m = mode_of(cfg->dtype);
+  const HeadPlan P = head_plan(d, m);
+  if (ws_bytes < P.total)
+    return fail(VTD_ERR_WORKSPACE, "head_backward: workspace too small (need " +
+                                       std::to_string(P.total) + " bytes)");
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(ws_);
+  const int op = m.op, R = (int)d.rows, HR = (int)d.head_rows, T = d.tokens, Tp = d.tokens_p;
+  const int D = d.d, Dp = d.d_p, act = cfg->use_mish ? VTD_ACT_MISH : VTD_ACT_GELU_TANH;
+  float* part = reinterpret_cast<float*>(ws + P.part);
+  float* bias = reinterpret_cast<float*>(ws + P.bias);
+  float* logits = logits_out ? logits_out : reinterpret_cast<float*>(ws + P.logits);
+  int rc;
+  // Keras kernel [K][N] -> W^T [Np][kk(Kp)] in the operand dtype (the forward GEMMs' Bt), pad
+  // rows and columns zero
+  auto conv_t = [&](const float* src, int K, int N, int Kp, int Np) -> int {
+    return transpose_op_launch(src, K, N, ws + P.wt, Kp, Np, op, st);
+  };
+  // Keras kernel [K][N] -> [Kp][kk(Np)] in the operand dtype (Bt of dA = dZ W^T): the rows as
+  // stored, pad rows and columns zero
+  auto conv_kn = [&](const float* src, int K, int N, int Kp, int Np) -> int {
+    void* dst = ws + P.wkn;
+    VTD_HIP(hipMemsetAsync(dst, 0, (size_t)Kp * m.kk(Np) * 2, st));
+    return m.x3 ? split_bf16x3_launch(src, K, N, N, dst, 3 * Np, 1, st)
+                : act_forward_launch(src, K, N, N, VTD_ACT_NONE, dst, Np, VTD_BF16, st);
+  };
+  auto pad_bias = [&](const float* b, int N, int Np) -> int {
+    VTD_HIP(hipMemsetAsync(bias, 0, (size_t)Np * 4, st));
+    VTD_HIP(hipMemcpyAsync(bias, b, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
+    return VTD_OK;
+  };
+  auto gemm = [&](int M, int N, int K, const void* A, int lda, const void* Bt, int ks,
+                  const vtd_epilogue& e, double fl) -> int {
+    return ks > 1 ? gemm_splitk_launch(M, N, K, A, lda, Bt, K, op, &e, part, ks, st, fl)
+                  : gemm_launch(M, N, K, A, lda, Bt, K, op, &e, st, fl);
+  };
+  auto wgrad = [&](int M, int K, int N, const void* X, int ldx, const void* G, int ldg, float* dW,
+                   float* db, int ms) -> int {
+    return gemm_wgrad_launch(M, K, N, X, ldx, G, ldg, op, dW, N, db, part, P.part_bytes, ms, st);
+  };
+
+  // ================= training forward from `encoded`: z and the activations are kept
+  void* a_enc = ws + P.a_enc;
+  void* u = ws + P.u;
+  if ((rc = act_forward_launch(encoded, R, D, D, VTD_ACT_NONE, a_enc, m.ka(Dp), op, st))) return rc;
+  {                                   // Dense(17) + Reshape as the scatter epilogue
+    if ((rc = conv_t(w->w_det, D, VTD_MAX_DETECT, Dp, 64))) return rc;
+    if ((rc = pad_bias(w->b_det, VTD_MAX_DETECT, 64))) return rc;
+    VTD_HIP(hipMemsetAsync(u, 0, (size_t)HR * Tp * m.eop, st));
+    vtd_epilogue e{};
+    e.bias = bias; e.act = VTD_ACT_NONE;
+    e.out = u; e.ldo = m.ka(Tp); e.out_dtype = op;
+    e.scatter_tokens = T;
+    if ((rc = gemm_launch(R, VTD_MAX_DETECT, m.kk(Dp), a_enc, m.ka(Dp), ws + P.wt, m.kk(Dp), op,
+                          &e, st, 2.0 * R * D * VTD_MAX_DETECT)))
+      return rc;
+  }
+  const void* a = u;
+  int k = Tp, kv = T;
+  for (int j = 0; j < nh; ++j) {
+    const int up = d.head_units_p[j], uv = d.head_units[j];
+    if ((rc = conv_t(w->w_head[j], kv, uv, k, up))) return rc;
+    if ((rc = pad_bias(w->b_head[j], uv, up))) return rc;
+    vtd_epilogue e{};
+    e.bias = bias; e.act = VTD_ACT_NONE;
+    e.out = ws + P.z[j]; e.ldo = up; e.out_dtype = VTD_F32;
+    if ((rc = gemm(HR, up, m.kk(k), a, m.ka(k), ws + P.wt, P.fwd_ks[j], e, 2.0 * HR * kv * uv)))
+      return rc;
+    if ((rc = act_forward_launch(reinterpret_cast<const float*>(ws + P.z[j]), HR, uv, up, act,
+                                 ws + P.a[j], m.ka(up), op, st)))
+      return rc;
+    a = ws + P.a[j];
+    k = up; kv = uv;
+  }
+  {                                   // MLP_Head_no_Sigmoid
+    if ((rc = conv_t(w->w_final, kv, 6, k, 64))) return rc;
+    if ((rc = pad_bias(w->b_final, 6, 64))) return rc;
+    vtd_epilogue e{};
+    e.bias = bias; e.act = VTD_ACT_NONE;
+    e.out = logits; e.ldo = 6; e.out_dtype = VTD_F32;
+    if ((rc = gemm_launch(HR, 6, m.kk(k), a, m.ka(k), ws + P.wt, m.kk(k), op, &e, st,
+                          2.0 * HR * kv * 6)))
+      return rc;
+  }
+
+  if (!dlogits) return VTD_OK;         // the training forward alone (logits_out)
+
+  // ================= backward
+  void* gf = ws + P.gf;
+  void* gz = ws + P.gz;
+  float* da[2] = {reinterpret_cast<float*>(ws + P.da[0]), reinterpret_cast<float*>(ws + P.da[1])};
+  if ((rc = act_forward_launch(dlogits, HR, 6, 6, VTD_ACT_NONE, gf, m.ka(64), op, st))) return rc;
+  if ((rc = wgrad(HR, kv, 6, a, m.ka(k), gf, m.ka(64), g->w_final, g->b_final, P.wg_ms[nh])))
+    return rc;
+  int cur = 0;                        // da[cur] = d loss / d (the activation feeding the layer above)
+  {
+    if ((rc = conv_kn(w->w_final, kv, 6, k, 64))) return rc;
+    vtd_epilogue e{};
+    e.act = VTD_ACT_NONE;
+    e.out = da[cur]; e.ldo = k; e.out_dtype = VTD_F32;
+    if ((rc = gemm(HR, k, m.kk(64), gf, m.ka(64), ws + P.wkn, P.bwd_ks[nh], e, 2.0 * HR * kv * 6)))
+      return rc;
+  }
+  for (int j = nh - 1; j >= 0; --j) {
+    const int up = d.head_units_p[j], uv = d.head_units[j];
+    const int kin = j ? d.head_units_p[j - 1] : Tp, kinv = j ? d.head_units[j - 1] : T;
+    const void* ain = j ? ws + P.a[j - 1] : u;
+    if ((rc = act_grad_launch(reinterpret_cast<const float*>(ws + P.z[j]), up, da[cur], up, HR, uv,
+                              act, gz, m.ka(up), op, st)))
+      return rc;
+    if ((rc = wgrad(HR, kinv, uv, ain, m.ka(kin), gz, m.ka(up), g->w_head[j], g->b_head[j],
+                    P.wg_ms[j])))
+      return rc;
+    if ((rc = conv_kn(w->w_head[j], kinv, uv, kin, up))) return rc;
+    vtd_epilogue e{};
+    e.act = VTD_ACT_NONE;
+    e.out = da[cur ^ 1]; e.ldo = kin; e.out_dtype = VTD_F32;
+    if ((rc = gemm(HR, kin, m.kk(up), gz, m.ka(up), ws + P.wkn, P.bwd_ks[j], e,
+                   2.0 * HR * kinv * uv)))
+      return rc;
+    cur ^= 1;
+  }
+  // da[cur] = dU [B 17][Tp]: back through the Reshape, then Dense(17)
+  void* dt = ws + P.dt;
+  if ((rc = head_unscatter_launch(da[cur], cfg->batch, T, Tp, dt, m.ka(64), op, st))) return rc;
+  if ((rc = wgrad(R, D, VTD_MAX_DETECT, a_enc, m.ka(Dp), dt, m.ka(64), g->w_det, g->b_det,
+                  P.wg_ms[nh + 1])))
+    return rc;
+  if (g->d_encoded) {
+    if ((rc = conv_kn(w->w_det, D, VTD_MAX_DETECT, Dp, 64))) return rc;
+    vtd_epilogue e{};
+    e.act = VTD_ACT_NONE;
+    e.out = g->d_encoded; e.ldo = D; e.out_dtype = VTD_F32;
+    if ((rc = gemm_launch(R, D, m.kk(64), dt, m.ka(64), ws + P.wkn, m.kk(64), op, &e, st,
+                          2.0 * R * D * VTD_MAX_DETECT)))
+      return rc;
+  }
+  return VTD_OK;
+}
+
+extern "C" {
+
+int vtd_forward(const vtd_config* cfg, const vtd_weights* w, const float* images,
+                float* logits, float* dets, void* workspace, size_t workspace_bytes,
+                void* stream_) {
+  return run_forward(cfg, w, images, logits, dets, nullptr, workspace, workspace_bytes, stream_);
+}
+
+int vtd_forward_encoded(const vtd_config* cfg, const vtd_weights* w, const float* images,
+                        float* encoded, void* workspace, size_t workspace_bytes, void* stream_) {
+  return run_forward(cfg, w, images, nullptr, nullptr, encoded, workspace, workspace_bytes,
+                     stream_);
+}
+
+int vtd_head_backward_workspace_bytes(const vtd_config* cfg, size_t* bytes) {
+  VTD_CHECK_ARG(bytes, "null bytes pointer");
+  vtd_dims d;
+  if (int rc = head_mode(cfg, &d, "head_backward_workspace_bytes")) return rc;
+  *bytes = head_plan(d, mode_of(cfg->dtype)).total;
+  return VTD_OK;
+}
+
+int vtd_head_backward(const vtd_config* cfg, const vtd_head_params* w, const float* encoded_dev,
+                      const float* dlogits_dev, float* logits_dev, const vtd_head_grads* g,
+                      void* ws, size_t ws_bytes, void* stream) {
+  return head_backward(cfg, w, encoded_dev, dlogits_dev, logits_dev, g, ws, ws_bytes, stream);
+}
+
 }  // extern "C"
 
 extern "C" {

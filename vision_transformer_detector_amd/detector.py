@@ -543,7 +543,7 @@ class Model:
         """The forward and the compiled loss with its gradient at the logits: (out5,
         d loss / d logits), both on the device, as loss.loss_and_grad(y_true, model(images),
         <the compiled keywords>) returns them -- where a backward pass through the model
-        would start.  Needs compile(loss=my_custom_loss or a functools.partial of it)."""
+        starts (head_gradients carries it through the detection head).  Needs compile(loss=my_custom_loss or a functools.partial of it)."""
         from . import loss as _loss
         params = _loss.fused_loss_params(self.loss) if self.loss is not None else None
         if params is None:
@@ -551,6 +551,102 @@ class Model:
                              "of it with keyword arguments) first")
         with torch.cuda.device(self.device):
             return _loss.loss_and_grad(y_true, self.forward(images), params=params)
+
+    # ---- head backward (vtd_forward_encoded, vtd_head_backward)
+    def encode(self, images, stream=None):
+        """Keras layer `encoded_images`: the encoder's output, the residual stream after the
+        last layer, as a (B, N, d) fp32 device tensor (vtd_forward_encoded: the forward's own
+        stages, without the head)."""
+        x = self._as_images(images)
+        b = x.shape[0]
+        out = torch.empty((b, self.dims.tokens, self.dims.d), dtype=torch.float32,
+                          device=self.device)
+        ws = self._workspace(b)
+        cfg = self.config(b)
+        with torch.cuda.device(self.device):
+            L.check(L.lib.vtd_forward_encoded(ctypes.byref(cfg), ctypes.byref(self._weights_c),
+                                              x.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                              ws.numel(), L.stream_ptr(stream)),
+                    "vtd_forward_encoded")
+        return out
+
+    def head_weight_names(self):
+        """The Keras weight names of the detection head, in `weight_names()` order."""
+        names = ["dense/kernel", "dense/bias"]
+        for j in range(self.dims.n_head):
+            names += [f"dense_{j + 1}/kernel", f"dense_{j + 1}/bias"]
+        return names + ["MLP_Head_no_Sigmoid/kernel", "MLP_Head_no_Sigmoid/bias"]
+
+    def _head_master(self):
+        """fp32 device copies of the head's weights in the Keras layout (vtd_head_params),
+        made once per set_weights."""
+        if getattr(self, "_head_dev_of", None) is not self._master:
+            self._head_dev = OrderedDict(
+                (n, self._master[n].to(self.device).contiguous()) for n in self.head_weight_names())
+            self._head_dev_of = self._master
+        return self._head_dev
+
+    def head_gradients(self, images, y_true, encoded=None):
+        """One frozen-encoder training step up to the optimizer update: encoder features ->
+        head -> compiled loss -> gradients.  Returns (out5, grads): out5 as loss_and_grad
+        returns it (total, objectness, class, CIoU means, positives) and `grads` an OrderedDict
+        of fp32 device tensors keyed by the head's Keras weight names (`head_weight_names()`)
+        plus "encoded_images" (B, N, d) = d loss / d encoded_images, where an encoder backward
+        would start.  `encoded`: the (B, N, d) output of `encode` -- the cached-features use,
+        `images` is then ignored.  The logits gradient is vtd_loss_grad's, the rest
+        vtd_head_backward.  Needs compile(loss=my_custom_loss or a functools.partial of it) and
+        dtype 'bf16x3' or 'bfloat16'."""
+        if self.dtype not in (L.BF16X3, L.BF16):
+            raise ValueError("head_gradients: the head backward runs in the 'bf16x3' and "
+                             "'bfloat16' modes only (not float32 / float8)")
+        from . import loss as _loss
+        params = _loss.fused_loss_params(self.loss) if self.loss is not None else None
+        if params is None:
+            raise ValueError("head_gradients: compile(loss=my_custom_loss or a functools.partial "
+                             "of it with keyword arguments) first")
+        dims = self.dims
+        with torch.cuda.device(self.device):
+            if encoded is None:
+                encoded = self.encode(images)
+            else:
+                encoded = torch.as_tensor(encoded).to(device=self.device,
+                                                      dtype=torch.float32).contiguous()
+                if encoded.dim() != 3 or tuple(encoded.shape[1:]) != (dims.tokens, dims.d):
+                    raise ValueError(f"head_gradients: encoded must be (B, {dims.tokens}, "
+                                     f"{dims.d}), got {tuple(encoded.shape)}")
+            b = encoded.shape[0]
+            cfg = self.config(b)
+            need = ctypes.c_size_t()
+            L.check(L.lib.vtd_head_backward_workspace_bytes(ctypes.byref(cfg), ctypes.byref(need)),
+                    "head_backward_workspace_bytes")
+            if getattr(self, "_hb_ws", None) is None or self._hb_ws.numel() < need.value:
+                self._hb_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            wdev = self._head_master()
+            grads = OrderedDict((n, torch.empty_like(t)) for n, t in wdev.items())
+            grads["encoded_images"] = torch.empty_like(encoded)
+            P, G = L.VtdHeadParams(), L.VtdHeadGrads()
+            for S, src in ((P, wdev), (G, grads)):
+                S.w_det, S.b_det = src["dense/kernel"].data_ptr(), src["dense/bias"].data_ptr()
+                for j in range(dims.n_head):
+                    S.w_head[j] = src[f"dense_{j + 1}/kernel"].data_ptr()
+                    S.b_head[j] = src[f"dense_{j + 1}/bias"].data_ptr()
+                S.w_final = src["MLP_Head_no_Sigmoid/kernel"].data_ptr()
+                S.b_final = src["MLP_Head_no_Sigmoid/bias"].data_ptr()
+            G.d_encoded = grads["encoded_images"].data_ptr()
+            st = L.stream_ptr()
+            # the training forward alone for its logits, the loss gradient at those logits,
+            # then the forward again with the backward
+            logits = torch.empty((b, L.MAX_DETECT, 6), dtype=torch.float32, device=self.device)
+            L.check(L.lib.vtd_head_backward(ctypes.byref(cfg), ctypes.byref(P), encoded.data_ptr(),
+                                            None, logits.data_ptr(), None,
+                                            self._hb_ws.data_ptr(), self._hb_ws.numel(), st),
+                    "vtd_head_backward")
+            out5, dlogits = _loss.loss_and_grad(y_true, logits, params=params)
+            L.check(L.lib.vtd_head_backward(ctypes.byref(cfg), ctypes.byref(P), encoded.data_ptr(),
+                                            dlogits.data_ptr(), None, ctypes.byref(G),
+                                            self._hb_ws.data_ptr(), self._hb_ws.numel(), st),
+                    "vtd_head_backward")
+        return out5, grads
 
     def count_params(self) -> int:
         return int(sum(int(np.prod(s)) for s in self.weight_shapes.values()))

@@ -9,8 +9,10 @@ per batch, fp32 per-slot arithmetic in the reference's order, fp64 fixed-order s
 prediction tensor requires grad (and grad mode is on) they run as torch.autograd.Functions
 over the analytic gradient kernels (vtd_loss_grad / vtd_ciou_grad / vtd_decode_grad, first
 derivatives only); otherwise they take the value-only path unchanged.  Labels are constants.
-`loss_and_grad` returns the values and d loss / d prediction without autograd.  Backward
-through the model, optimizers and `fit` are out of scope.  `get_label_arrays` (host only)
+`loss_and_grad` returns the values and d loss / d prediction without autograd; from there
+`Model.head_gradients` carries the gradient back through the detection head (vtd_head_backward:
+the head's weight gradients and d loss / d encoded_images).  Backward through the encoder,
+optimizers and `fit` are out of scope.  `get_label_arrays` (host only)
 builds the reference's label rows (vision_transformer_utilities.py:268-382, 452-507).
 """
 from __future__ import annotations
