@@ -191,7 +191,11 @@ int vtd_extract_patches(const float* images_dev, int B, int H, int W, int C, int
  * [hi | lo], two ldo / 2 wide pieces, ldo % 2 == 0, ldo / 2 >= N; bf16 / split-bf16
  * operands only); out2 (nullable) a second bf16 copy.
  * scatter_tokens > 0 selects the head Reshape epilogue (vtd.py:461-463): element
- * (m = b*T + t, n < 17) is stored at out[(b*17 + f / T) * ldo + f % T], f = t*17 + n. */
+ * (m = b*T + t, n < 17) is stored at out[(b*17 + f / T) * ldo + f % T], f = t*17 + n.
+ * Pad rule: no value outside the M x K / N x K operand elements (and the epilogue vectors'
+ * M, N or period entries) reaches an output, and nothing but the M x N output elements (of
+ * every piece) is written -- pad columns up to the leading dimensions and neighbouring memory
+ * keep their bytes (tests/test_gpu_gemm_designed.py runs every kernel inside guard bands). */
 typedef struct vtd_epilogue {
   const float* bias;            /* [N] or NULL                                    */
   const float* rowadd;          /* position embedding per row, or NULL            */
