@@ -634,6 +634,52 @@ int vtd_head_backward(const vtd_config* cfg, const vtd_head_params* w, const flo
                       const float* dlogits_dev, float* logits_dev, const vtd_head_grads* g,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* ---- optimizer step: keras.optimizers.Adam + the ClipWeight constraint + the operand re-pack
+ * One tensor of the table: w, m, v (updated in place) and g (read only), fp32 device arrays
+ * in the Keras layout with 16-B aligned bases.  VTD_ADAM_MATRIX: a kernel [K][N] row-major;
+ * `packed` (nullable: update the master only) is the forward's operand W^T [N_p][ld] of it --
+ * VTD_BF16: bf16 rows, K_p = ld; VTD_BF16X3: the split-bf16 B operand [hi | hi | lo] with
+ * piece width K_p = ld / 3 -- 16-B aligned, K_p >= K, K_p % 8 == 0.  VTD_ADAM_VECTOR: a bias
+ * [N] (K and ld unused); `packed` (nullable) is the fp32 padded vector vtd_pack_vector writes.
+ * Padding rule: for rows n < N of a matrix's operand the step writes columns [0, K_p) of each
+ * piece, zeros in [K, K_p), and for a vector elements [0, N); rows >= N, elements >= N and
+ * everything outside the buffers stay untouched. */
+enum { VTD_ADAM_MATRIX = 0, VTD_ADAM_VECTOR = 1 };
+typedef struct vtd_adam_tensor {
+  float* w; float* m; float* v; const float* g;
+  void* packed;
+  int kind, K, N, ld;
+} vtd_adam_tensor;
+/* The plan: the table in its device form plus a tile -> tensor map, built and uploaded ONCE
+ * per optimizer state into caller-owned device memory (plan_dev, 16-B aligned, plan_bytes >=
+ * what vtd_adam_plan_bytes returns; *tiles is the grid vtd_adam_step launches).  `tensors` is
+ * a host array.  vtd_adam_plan_upload copies on `stream` and waits for the copy (the only
+ * synchronising entry of the three).  `dtype`: the packed operands' mode.
+ * VTD_ERR_INVALID_ARG before any device call: null pointers (the table, w / m / v / g, the
+ * outputs, plan_dev), non-positive sizes, misaligned bases, and for a packed destination a
+ * dtype other than VTD_BF16 / VTD_BF16X3, ld % 3 != 0 in VTD_BF16X3, ld too small (K_p < K),
+ * K_p % 8 != 0; plan_bytes too small. */
+int vtd_adam_plan_bytes(const vtd_adam_tensor* tensors, int n_tensors, int dtype, size_t* bytes,
+                        int* tiles);
+int vtd_adam_plan_upload(const vtd_adam_tensor* tensors, int n_tensors, int dtype,
+                         void* plan_dev, size_t plan_bytes, void* stream);
+/* Step t (1, 2, ...) of every tensor of the plan in ONE launch, per element in fp32 and in this
+ * order (TF's ApplyAdam functor; every operation rounded once, no FMA contraction):
+ *   g  = clipvalue > 0 ? clip(g, -clipvalue, +clipvalue) : g        (a NaN passes through)
+ *   m += (g - m) * (1 - beta1);   v += (g * g - v) * (1 - beta2)
+ *   w -= (m * alpha) / (sqrt(v) + epsilon)
+ *   w  = constrain ? clip(isnan(w) ? 1.0 : w, -max_weight, +max_weight) : w     (ClipWeight)
+ * alpha = learning_rate sqrt(1 - beta2^t) / (1 - beta1^t) is formed on the host in double (from
+ * the fp32 betas) and rounded to fp32 once; 1 - beta in fp32.  The packed destinations receive
+ * the new w through the conversions of vtd_pack_dense / vtd_split_bf16x3 (role 1): the same
+ * bytes as those calls on the updated master.  n_tensors and tiles: as given to / returned by
+ * the plan entries.  Asynchronous on `stream`; no copy, no allocation, no host synchronisation;
+ * no atomics, bit-identical from run to run.  VTD_ERR_INVALID_ARG before any device call: a
+ * null plan, non-positive n_tensors / tiles, t < 1, constrain with max_weight <= 0. */
+int vtd_adam_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
+                  double learning_rate, float beta1, float beta2, float epsilon, float clipvalue,
+                  int constrain, float max_weight, void* stream);
+
 /* Optional per-kernel timing of vtd_forward (hipEvents on `stream`, recorded around
  * every launch while enabled).  vtd_profile_read returns per-class totals in ms
  * summed over the forwards since the last reset; classes: 0 gemm, 1 attention,

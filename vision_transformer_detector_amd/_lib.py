@@ -100,6 +100,14 @@ class VtdHeadGrads(ctypes.Structure):
     _fields_ = VtdHeadParams._fields_ + [("d_encoded", c_void_p)]
 
 
+ADAM_MATRIX, ADAM_VECTOR = 0, 1
+
+
+class VtdAdamTensor(ctypes.Structure):
+    _fields_ = [("w", c_void_p), ("m", c_void_p), ("v", c_void_p), ("g", c_void_p),
+                ("packed", c_void_p), ("kind", c_int), ("K", c_int), ("N", c_int), ("ld", c_int)]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "vtd_abi_version": (c_int, []),
@@ -190,6 +198,12 @@ SIGNATURES = {
     "vtd_head_backward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdHeadParams),
                                   c_void_p, c_void_p, c_void_p, ctypes.POINTER(VtdHeadGrads),
                                   c_void_p, c_size_t, c_void_p]),
+    "vtd_adam_plan_bytes": (c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int,
+                                    ctypes.POINTER(c_size_t), ctypes.POINTER(c_int)]),
+    "vtd_adam_plan_upload": (c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int, c_void_p,
+                                     c_size_t, c_void_p]),
+    "vtd_adam_step": (c_int, [c_void_p, c_int, c_int, c_int64, ctypes.c_double, c_float, c_float,
+                              c_float, c_float, c_int, c_float, c_void_p]),
     "vtd_forward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdWeights), c_void_p,
                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vtd_set_knob": (c_int, [c_int, c_int]),

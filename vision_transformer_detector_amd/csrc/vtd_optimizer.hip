@@ -1,0 +1,307 @@
+// Adam step of keras.optimizers.Adam (TF's ApplyAdam functor order) fused with the ClipWeight
+// constraint (vtd.py:209-236) and with the re-pack of the forward's operands: one launch per
+// training step over a table of tensors (vtd_adam_plan_upload, vtd_adam_step; include/vtd.h).
+//
+// This file is compiled with -ffp-contract=off (Makefile) and with hipcc's correctly rounded
+// fp32 sqrt and division: every operation below is one IEEE fp32 operation, in the order
+// written, so the result is bit-identical to a numpy float32 restatement
+// (tests/adam_oracle.py step32).  The clips are comparisons: fminf / fmaxf drop a NaN and
+// tf.clip_by_value does not.
+//
+// Work unit: a tile of 64 (K) x 64 (N) of one matrix, 256 threads, or 256 elements of a vector.
+// The plan holds the tensor descriptors and a tile -> (tensor, tile in tensor) map; workgroup b
+// takes map[b].  Every element belongs to exactly one thread: no atomics, the same bits on
+// every run.
+//
+//   phase 1 (coalesced along N, the Keras layout's contiguous axis): each thread takes V
+//     consecutive columns of one row, V = 4 / 2 / 1 the widest vector that every row start of
+//     the tensor is aligned for (N % V == 0; the bases are 16-B aligned) -- 64 / V threads per
+//     tile row, 4 V rows per pass, 16 / V passes.  It reads w, m, v, g, updates, writes w, m, v
+//     back and leaves the new w in LDS; elements outside the matrix leave 0 there.
+//   phase 2 (coalesced along K, the packed layout's contiguous axis): each thread takes 8
+//     consecutive k of one column n, converts them with the conversions vtd_pack_dense /
+//     vtd_split_bf16x3 use (pack_bf16x2, pack_lo_bf16x2) and stores 16 B per piece: the 8
+//     threads of a column write one whole 128-B run, a wave 8 columns.
+//
+// LDS layout: float tile[64][65], element (k, n) at word 65 k + n.  gfx950's LDS has 64 banks
+// of 4 B, bank = word mod 64 = (k + n) mod 64 since 65 = 1 (mod 64).
+//   phase-1 writes (4-B, one per column of the thread): a wave holds V tile rows; for a fixed j
+//     lane l writes column V c + j (c = l mod (64 / V)) of row r0 + q (q = l / (64 / V) < V):
+//     banks (r0 + j + q + V c) mod 64, and q + V c is a bijection onto [0, 64): no two lanes
+//     share a bank.
+//   phase-2 reads (4-B): lane l reads (8 (l & 7) + j, n0 + (l >> 3)) for j = 0 .. 7: banks
+//     (8 (l & 7) + (l >> 3) + j + n0) mod 64, and 8 a + b with a, b < 8 is a bijection onto
+//     [0, 64): conflict-free.
+// A pitch of 64 would put the whole phase-2 read of a wave on 8 banks (8-way conflict).
+//
+// Padding rule: for columns n < N the kernel writes [0, K_p) of each piece of packed row n
+// (K_p = ld, or ld / 3 in split-bf16), zeros in [K, K_p); rows >= N and everything outside the
+// buffers stay untouched.  A vector writes elements [0, N) of its fp32 destination.
+#include "vtd_common.h"
+
+#include <cmath>
+#include <vector>
+
+namespace vtd {
+namespace {
+
+constexpr int kTile = 64;           // tile edge (K and N)
+constexpr int kPitch = kTile + 1;   // LDS row pitch in words (see above)
+constexpr int kThreads = 256;
+constexpr int kVecTile = 256;       // elements of a vector per workgroup
+
+// device form of vtd_adam_tensor plus what the plan derives from it
+struct AdamDesc {
+  float* w; float* m; float* v; const float* g;
+  void* packed;
+  int kind, K, N, ld;
+  int kp;        // piece width of a packed row (matrix)
+  int ntn;       // tiles along N (matrix)
+  int vec;       // 4 / 2 / 1: columns per thread in phase 1
+  int x3;        // packed rows are split-bf16 [hi | hi | lo]
+};
+struct AdamScalars {
+  float alpha, beta1, beta2, epsilon, clipvalue, max_weight;
+  int constrain;
+};
+
+// The table's pointers are loaded from memory, so the compiler cannot tell their address space
+// and would use flat_* accesses; they are device-memory pointers: global_* loads and stores.
+template <class T> using gptr = __attribute__((address_space(1))) T*;
+template <class T> __device__ __forceinline__ gptr<T> as_global(T* p) {
+  return (gptr<T>)p;
+}
+
+__device__ __forceinline__ float clip(float x, float lo, float hi) {
+  return x < lo ? lo : (x > hi ? hi : x);          // NaN passes through
+}
+
+// one element; returns the new w
+__device__ __forceinline__ float adam_element(float w, float& m, float& v, float g,
+                                              const AdamScalars& s) {
+  if (s.clipvalue > 0.f) g = clip(g, -s.clipvalue, s.clipvalue);
+  const float omb1 = 1.f - s.beta1, omb2 = 1.f - s.beta2;
+  m = m + (g - m) * omb1;
+  v = v + (g * g - v) * omb2;
+  w = w - (m * s.alpha) / (sqrtf(v) + s.epsilon);
+  if (s.constrain) w = clip(w != w ? 1.f : w, -s.max_weight, s.max_weight);
+  return w;
+}
+
+template <int V>
+__device__ __forceinline__ void matrix_phase1(const AdamDesc& d, const AdamScalars& s, int k0,
+                                              int n0, float (*tile)[kPitch]) {
+  typedef float vecf __attribute__((ext_vector_type(V)));
+  const gptr<float> pw = as_global(d.w), pm = as_global(d.m), pv = as_global(d.v);
+  const gptr<const float> pg = as_global(d.g);
+  constexpr int kTpr = kTile / V;                  // threads per tile row
+  constexpr int kRpp = kThreads / kTpr;            // rows per pass
+  const int c = (threadIdx.x % kTpr) * V, r = threadIdx.x / kTpr;
+#pragma unroll 2
+  for (int p = 0; p < kTile / kRpp; ++p) {
+    const int kk = p * kRpp + r, k = k0 + kk, n = n0 + c;
+    float out[V];
+    if (k < d.K && n < d.N) {                      // N % V == 0: all V columns or none
+      const int64_t at = (int64_t)k * d.N + n;
+      float wv[V], mv[V], vv[V], gv[V];
+      if constexpr (V == 1) {
+        wv[0] = pw[at]; mv[0] = pm[at]; vv[0] = pv[at]; gv[0] = pg[at];
+      } else {
+        const vecf a = *(gptr<const vecf>)(pw + at);
+        const vecf b = *(gptr<const vecf>)(pm + at);
+        const vecf e = *(gptr<const vecf>)(pv + at);
+        const vecf f = *(gptr<const vecf>)(pg + at);
+#pragma unroll
+        for (int j = 0; j < V; ++j) { wv[j] = a[j]; mv[j] = b[j]; vv[j] = e[j]; gv[j] = f[j]; }
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j) out[j] = adam_element(wv[j], mv[j], vv[j], gv[j], s);
+      if constexpr (V == 1) {
+        pw[at] = out[0]; pm[at] = mv[0]; pv[at] = vv[0];
+      } else {
+        vecf a, b, e;
+#pragma unroll
+        for (int j = 0; j < V; ++j) { a[j] = out[j]; b[j] = mv[j]; e[j] = vv[j]; }
+        *(gptr<vecf>)(pw + at) = a;
+        *(gptr<vecf>)(pm + at) = b;
+        *(gptr<vecf>)(pv + at) = e;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) out[j] = 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) tile[kk][c + j] = out[j];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void adam_step_kernel(const AdamDesc* __restrict__ descs,
+                                                            const int2* __restrict__ map,
+                                                            AdamScalars s) {
+  __shared__ float tile[kTile][kPitch];
+  const int2 where = map[blockIdx.x];
+  const AdamDesc d = descs[where.x];
+  if (d.kind == VTD_ADAM_VECTOR) {
+    const int n = where.y * kVecTile + threadIdx.x;
+    if (n < d.N) {
+      const gptr<float> pw = as_global(d.w), pm = as_global(d.m), pv = as_global(d.v);
+      float m = pm[n], v = pv[n];
+      const float w = adam_element(pw[n], m, v, as_global(d.g)[n], s);
+      pw[n] = w; pm[n] = m; pv[n] = v;
+      if (d.packed) as_global(static_cast<float*>(d.packed))[n] = w;
+    }
+    return;
+  }
+  const int k0 = (where.y / d.ntn) * kTile, n0 = (where.y % d.ntn) * kTile;
+  if (k0 < d.K) {                                   // a K tile past K only writes zero padding
+    if (d.vec == 4) matrix_phase1<4>(d, s, k0, n0, tile);
+    else if (d.vec == 2) matrix_phase1<2>(d, s, k0, n0, tile);
+    else matrix_phase1<1>(d, s, k0, n0, tile);
+  }
+  if (!d.packed) return;                            // uniform per workgroup
+  __syncthreads();
+  const gptr<bf16_t> dst = as_global(static_cast<bf16_t*>(d.packed));
+  const int kc = k0 + 8 * (threadIdx.x & 7);
+#pragma unroll
+  for (int p = 0; p < kTile / (kThreads / 8); ++p) {
+    const int nn = p * (kThreads / 8) + (threadIdx.x >> 3), n = n0 + nn;
+    if (n >= d.N || kc >= d.kp) continue;           // kp % 8 == 0: all 8 or none
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = k0 < d.K ? tile[kc - k0 + j][nn] : 0.f;
+    const uint32_t h0 = pack_bf16x2(v[0], v[1]), h1 = pack_bf16x2(v[2], v[3]),
+                   h2 = pack_bf16x2(v[4], v[5]), h3 = pack_bf16x2(v[6], v[7]);
+    const i32x4 hi = {(int)h0, (int)h1, (int)h2, (int)h3};
+    const gptr<bf16_t> row = dst + (int64_t)n * d.ld + kc;
+    *(gptr<i32x4>)row = hi;
+    if (d.x3) {                                     // B operand [hi | hi | lo]
+      const i32x4 lo = {(int)pack_lo_bf16x2(v[0], v[1], h0), (int)pack_lo_bf16x2(v[2], v[3], h1),
+                        (int)pack_lo_bf16x2(v[4], v[5], h2), (int)pack_lo_bf16x2(v[6], v[7], h3)};
+      *(gptr<i32x4>)(row + d.kp) = hi;
+      *(gptr<i32x4>)(row + 2 * d.kp) = lo;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ plan (host)
+int check_tensors(const vtd_adam_tensor* t, int n, int dtype, const char* what) {
+  const std::string w(what);
+  VTD_CHECK_ARG(t, w + ": null tensor table");
+  VTD_CHECK_ARG(n > 0, w + ": n_tensors must be positive");
+  for (int i = 0; i < n; ++i) {
+    const vtd_adam_tensor& a = t[i];
+    const std::string at = w + ": tensor " + std::to_string(i);
+    VTD_CHECK_ARG(a.w && a.m && a.v && a.g, at + ": null pointer (w, m, v, g)");
+    VTD_CHECK_ARG(a.kind == VTD_ADAM_MATRIX || a.kind == VTD_ADAM_VECTOR, at + ": bad kind");
+    VTD_CHECK_ARG(a.N > 0 && (a.kind == VTD_ADAM_VECTOR || a.K > 0),
+                  at + ": non-positive size");
+    for (const void* p : {(const void*)a.w, (const void*)a.m, (const void*)a.v,
+                          (const void*)a.g})
+      VTD_CHECK_ARG(reinterpret_cast<uintptr_t>(p) % 16 == 0, at + ": w, m, v, g need 16-B "
+                    "aligned bases");
+    if (!a.packed) continue;
+    VTD_CHECK_ARG(dtype == VTD_BF16 || dtype == VTD_BF16X3,
+                  at + ": a packed destination needs dtype VTD_BF16 or VTD_BF16X3");
+    if (a.kind == VTD_ADAM_VECTOR) continue;          // fp32 [N], ld unused
+    VTD_CHECK_ARG(dtype != VTD_BF16X3 || a.ld % 3 == 0,
+                  at + ": ld must be a multiple of 3 in split-bf16 (ld = 3 K_p)");
+    const int kp = dtype == VTD_BF16X3 ? a.ld / 3 : a.ld;
+    VTD_CHECK_ARG(kp >= a.K, at + ": ld too small (K_p < K)");
+    VTD_CHECK_ARG(kp % 8 == 0 && reinterpret_cast<uintptr_t>(a.packed) % 16 == 0,
+                  at + ": packed rows are written 16 B at a time: K_p % 8 == 0 and a 16-B "
+                  "aligned base");
+  }
+  return VTD_OK;
+}
+
+int tensor_tiles(const vtd_adam_tensor& a, int dtype, int* ntn, int* kp_out) {
+  if (a.kind == VTD_ADAM_VECTOR) { *ntn = 1; *kp_out = 0; return (a.N + kVecTile - 1) / kVecTile; }
+  // with a packed destination the K tiles run to K_p, so that [K, K_p) is zeroed
+  const int kp = a.packed ? (dtype == VTD_BF16X3 ? a.ld / 3 : a.ld) : a.K;
+  *ntn = (a.N + kTile - 1) / kTile;
+  *kp_out = kp;
+  return ((kp + kTile - 1) / kTile) * *ntn;
+}
+
+size_t plan_bytes(int n, int64_t tiles) {
+  return (size_t)round_up((int64_t)n * sizeof(AdamDesc), 16) + (size_t)tiles * sizeof(int2);
+}
+
+}  // namespace
+}  // namespace vtd
+
+extern "C" {
+
+int vtd_adam_plan_bytes(const vtd_adam_tensor* tensors, int n_tensors, int dtype, size_t* bytes,
+                        int* tiles) {
+  VTD_CHECK_ARG(bytes && tiles, "adam_plan_bytes: null output");
+  if (int rc = vtd::check_tensors(tensors, n_tensors, dtype, "adam_plan_bytes")) return rc;
+  int64_t total = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    int ntn, kp;
+    total += vtd::tensor_tiles(tensors[i], dtype, &ntn, &kp);
+  }
+  VTD_CHECK_ARG(total <= 0x7fffffff, "adam_plan_bytes: too many tiles");
+  *tiles = (int)total;
+  *bytes = vtd::plan_bytes(n_tensors, total);
+  return VTD_OK;
+}
+
+int vtd_adam_plan_upload(const vtd_adam_tensor* tensors, int n_tensors, int dtype,
+                         void* plan_dev, size_t plan_bytes, void* stream) {
+  size_t need = 0;
+  int tiles = 0;
+  if (int rc = vtd_adam_plan_bytes(tensors, n_tensors, dtype, &need, &tiles)) return rc;
+  VTD_CHECK_ARG(plan_dev, "adam_plan_upload: null plan_dev");
+  VTD_CHECK_ARG(reinterpret_cast<uintptr_t>(plan_dev) % 16 == 0,
+                "adam_plan_upload: plan_dev needs a 16-B aligned base");
+  VTD_CHECK_ARG(plan_bytes >= need, "adam_plan_upload: plan_bytes too small");
+  std::vector<char> host(need, 0);
+  vtd::AdamDesc* d = reinterpret_cast<vtd::AdamDesc*>(host.data());
+  int2* map = reinterpret_cast<int2*>(host.data() +
+                                      vtd::round_up((int64_t)n_tensors * sizeof(vtd::AdamDesc), 16));
+  int at = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const vtd_adam_tensor& a = tensors[i];
+    int ntn, kp;
+    const int nt = vtd::tensor_tiles(a, dtype, &ntn, &kp);
+    d[i].w = a.w; d[i].m = a.m; d[i].v = a.v; d[i].g = a.g; d[i].packed = a.packed;
+    d[i].kind = a.kind; d[i].K = a.kind == VTD_ADAM_VECTOR ? 1 : a.K; d[i].N = a.N;
+    d[i].ld = a.ld; d[i].kp = kp; d[i].ntn = ntn;
+    d[i].vec = a.N % 4 == 0 ? 4 : (a.N % 2 == 0 ? 2 : 1);
+    d[i].x3 = dtype == VTD_BF16X3 ? 1 : 0;
+    for (int t = 0; t < nt; ++t) map[at++] = int2{i, t};
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  VTD_HIP(hipMemcpyAsync(plan_dev, host.data(), need, hipMemcpyHostToDevice, st));
+  VTD_HIP(hipStreamSynchronize(st));                 // `host` goes out of scope
+  return VTD_OK;
+}
+
+int vtd_adam_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
+                  double learning_rate, float beta1, float beta2, float epsilon, float clipvalue,
+                  int constrain, float max_weight, void* stream) {
+  VTD_CHECK_ARG(plan_dev, "adam_step: null plan_dev");
+  VTD_CHECK_ARG(n_tensors > 0 && tiles > 0, "adam_step: non-positive n_tensors / tiles");
+  VTD_CHECK_ARG(t >= 1, "adam_step: t (the step number) starts at 1");
+  VTD_CHECK_ARG(!constrain || max_weight > 0.f, "adam_step: max_weight must be positive");
+  // alpha = lr sqrt(1 - beta2^t) / (1 - beta1^t) in double from the fp32 betas, rounded once
+  const double b1 = beta1, b2 = beta2;
+  vtd::AdamScalars s;
+  s.alpha = (float)(learning_rate * std::sqrt(1.0 - std::pow(b2, (double)t)) /
+                    (1.0 - std::pow(b1, (double)t)));
+  s.beta1 = beta1; s.beta2 = beta2; s.epsilon = epsilon;
+  s.clipvalue = clipvalue > 0.f ? clipvalue : 0.f;   // <= 0 or NaN: no gradient clip
+  s.max_weight = max_weight; s.constrain = constrain ? 1 : 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  vtd::ProfScope ps(st, vtd::PROF_OTHER, 0.0);
+  const char* base = static_cast<const char*>(plan_dev);
+  const int2* map = reinterpret_cast<const int2*>(
+      base + vtd::round_up((int64_t)n_tensors * sizeof(vtd::AdamDesc), 16));
+  hipLaunchKernelGGL(vtd::adam_step_kernel, dim3((unsigned)tiles), dim3(vtd::kThreads), 0, st,
+                     reinterpret_cast<const vtd::AdamDesc*>(base), map, s);
+  VTD_LAUNCH_CHECK("adam_step");
+  return VTD_OK;
+}
+
+}  // extern "C"

@@ -158,6 +158,8 @@ class Model:
         self._ws_bytes = 0
         self.loss = None               # compile(): the loss callable and the metric objects
         self.metrics = []
+        self.optimizer = None          # compile(): stored as given, resolved by a training call
+        self._head_dirty = False       # the head's device masters are ahead of self._master
         self.set_weights(keras_default_init(self.weight_shapes, seed))
 
     # ---- config helpers
@@ -177,12 +179,22 @@ class Model:
     # ---- weights
     def get_weights(self):
         """Weights as a list in Keras creation order (names: `weight_names()`)."""
+        self._sync_master()
         return [self._master[n].numpy().copy() for n in self.weight_shapes]
 
     def weight_names(self):
         return list(self.weight_shapes)
 
+    def _sync_master(self):
+        """After optimizer steps the head's device masters are the truth: read them back into
+        the fp32 CPU masters (once per run of steps; the encoder's entries are untouched)."""
+        if self._head_dirty:
+            for n, t in self._head_master().items():
+                self._master[n] = t.cpu()
+            self._head_dirty = False
+
     def get_weight_dict(self):
+        self._sync_master()
         return OrderedDict((n, self._master[n].numpy().copy()) for n in self.weight_shapes)
 
     def set_weights(self, weights):
@@ -207,12 +219,16 @@ class Model:
                                  f"{self.weight_shapes[n]}")
             master[n] = t.contiguous()
         self._master = master
+        self._head_dirty = False
         self._pack()
+        if hasattr(self.optimizer, "_reset"):       # its table points at the old device masters
+            self.optimizer._reset(self)
 
     # ---- weight files (Keras-name keyed; see tools/keras_weights_to_npz.py)
     def save_weights(self, path: str) -> None:
         """Write the fp32 master weights keyed by Keras weight names to `.npz` or
         `.safetensors` (the interchange format of this package)."""
+        self._sync_master()
         d = {n: t.numpy() for n, t in self._master.items()}
         if path.endswith(".safetensors"):
             from safetensors.numpy import save_file
@@ -246,6 +262,7 @@ class Model:
         tdt = _TORCH_DTYPE[dt]
         dev = self.device
         keep, staging = [], []
+        head = {}        # Keras name -> packed tensor of the head (vtd_adam_step re-packs them)
         stream = L.stream_ptr(torch.cuda.current_stream(dev))
 
         def zeros(*shape, dtype=tdt):
@@ -386,19 +403,25 @@ class Model:
                     Ly.b_mlp[j] = bm.data_ptr()
                 k_p = n_p
         W.layers = ctypes.cast(layers, ctypes.POINTER(L.VtdLayerWeights))
-        W.w_det = dense("dense", L.KALIGN, dims.d_p).data_ptr()
-        W.b_det = vector("dense/bias", L.KALIGN).data_ptr()
+        head["dense/kernel"] = dense("dense", L.KALIGN, dims.d_p)
+        head["dense/bias"] = vector("dense/bias", L.KALIGN)
+        W.w_det, W.b_det = head["dense/kernel"].data_ptr(), head["dense/bias"].data_ptr()
         k_p = dims.tokens_p
         for j in range(dims.n_head):
             n_p = dims.head_units_p[j]
-            W.w_head[j] = dense(f"dense_{j + 1}", n_p, k_p).data_ptr()
-            W.b_head[j] = vector(f"dense_{j + 1}/bias", n_p).data_ptr()
+            head[f"dense_{j + 1}/kernel"] = dense(f"dense_{j + 1}", n_p, k_p)
+            head[f"dense_{j + 1}/bias"] = vector(f"dense_{j + 1}/bias", n_p)
+            W.w_head[j] = head[f"dense_{j + 1}/kernel"].data_ptr()
+            W.b_head[j] = head[f"dense_{j + 1}/bias"].data_ptr()
             k_p = n_p
-        W.w_final = dense("MLP_Head_no_Sigmoid", L.KALIGN, k_p).data_ptr()
-        W.b_final = vector("MLP_Head_no_Sigmoid/bias", L.KALIGN).data_ptr()
+        head["MLP_Head_no_Sigmoid/kernel"] = dense("MLP_Head_no_Sigmoid", L.KALIGN, k_p)
+        head["MLP_Head_no_Sigmoid/bias"] = vector("MLP_Head_no_Sigmoid/bias", L.KALIGN)
+        W.w_final = head["MLP_Head_no_Sigmoid/kernel"].data_ptr()
+        W.b_final = head["MLP_Head_no_Sigmoid/bias"].data_ptr()
         torch.cuda.current_stream(dev).synchronize()
         del staging      # fp32 staging copies; the packed buffers stay alive in `keep`
         self._packed = keep
+        self._head_packed = head
         self._layers_c = layers
         self._weights_c = W
 
@@ -462,12 +485,13 @@ class Model:
 
     # ---- compile / evaluate (ipynb:408-435, 835; vtd.py:2172)
     def compile(self, optimizer=None, loss=None, metrics=None, **_):
-        """keras.Model.compile for the evaluation path: stores `loss` and `metrics`;
-        `optimizer` is ignored (inference only).  `loss` is my_custom_loss or a
+        """keras.Model.compile: stores `optimizer`, `loss` and `metrics`.  `optimizer` is kept as
+        given and never refused here -- optimizers.Adam or the string "adam" (= Adam()) train the
+        head (train_head_on_batch, fit_head); anything else raises only when a training call
+        needs it.  `loss` is my_custom_loss or a
         functools.partial of it (its keywords are read off and evaluate runs the fused
         from-logits kernel), or any callable (y_true, logits) -> scalar, called per batch.
         `metrics`: objects with update_state / result / reset_state (MeanAveragePrecision)."""
-        del optimizer
         if loss is not None and not callable(loss):
             raise TypeError(f"compile: loss must be callable, got {type(loss).__name__}")
         metrics = list(metrics or [])
@@ -475,7 +499,10 @@ class Model:
             if not all(callable(getattr(m, a, None)) for a in ("update_state", "result",
                                                                "reset_state")):
                 raise TypeError(f"compile: metric {m!r} needs update_state / result / reset_state")
-        self.loss, self.metrics = loss, metrics
+        if isinstance(optimizer, str) and optimizer.lower() == "adam":
+            from .optimizers import Adam
+            optimizer = Adam()
+        self.loss, self.metrics, self.optimizer = loss, metrics, optimizer
 
     def _evaluate_batches(self, x, y, batch_size):
         if y is None:
@@ -596,13 +623,105 @@ class Model:
         `images` is then ignored.  The logits gradient is vtd_loss_grad's, the rest
         vtd_head_backward.  Needs compile(loss=my_custom_loss or a functools.partial of it) and
         dtype 'bf16x3' or 'bfloat16'."""
+        return self._head_pass("head_gradients", images, y_true, encoded)
+
+    # ---- head training (vtd_adam_step; optimizers.py)
+    def train_head_on_batch(self, images, y_true, encoded=None):
+        """keras.Model.train_on_batch for the detection head on a frozen encoder: head_gradients'
+        pass with the weight gradients written into the compiled optimizer's persistent buffers,
+        then ONE vtd_adam_step launch -- Adam, the ClipWeight constraint (`max_weight` /
+        `clip_weight` of the model's kwargs) and the re-pack of the forward's head operands.
+        Returns out5 as head_gradients does, taken before the update, as Keras reports the
+        loss; nothing is read back to the host.  Afterwards the device masters
+        (`_head_master()`) are the truth for the head; get_weights / get_weight_dict /
+        save_weights read them back on demand.  Needs compile(optimizer=optimizers.Adam(...) or
+        'adam', loss=my_custom_loss or a functools.partial of it) and dtype 'bf16x3' or
+        'bfloat16'."""
         if self.dtype not in (L.BF16X3, L.BF16):
-            raise ValueError("head_gradients: the head backward runs in the 'bf16x3' and "
+            raise ValueError("train_head_on_batch: the head backward runs in the 'bf16x3' and "
+                             "'bfloat16' modes only (not float32 / float8)")
+        from . import optimizers as _opt
+        try:
+            optimizer = _opt.resolve(self.optimizer)
+        except ValueError as e:
+            raise ValueError(f"train_head_on_batch: {e}") from None
+        out5, _ = self._head_pass("train_head_on_batch", images, y_true, encoded,
+                                  weight_grads=optimizer.gradient_buffers(self))
+        optimizer.apply(self)
+        return out5
+
+    def fit_head(self, x, y=None, batch_size=32, epochs=1, lr_schedule=None, cache_features=True,
+                 encoded=None):
+        """keras.Model.fit for the detection head on a frozen encoder (the notebook's "overfit
+        a few images" loop): `epochs` passes of train_head_on_batch over the batches, which are
+        formed as `evaluate` forms them (arrays split by `batch_size`, the last may be short; or
+        y=None and `x` a re-iterable of (images, labels) batches).  `lr_schedule(epoch, lr) ->
+        lr` is called at the start of every epoch with the optimizer's current rate, as
+        keras.callbacks.LearningRateScheduler calls it, and its return becomes the rate.
+        `cache_features`: the encoder runs once per batch and later epochs reuse its (B, N, d)
+        features (the encoder is frozen, so they cannot change).  `encoded`: the features of
+        the whole of `x` (len(x), N, d), as head_gradients takes them; `x` is then not read.
+        Returns an object whose .history["loss"] holds one float per epoch: the mean of the
+        batch losses weighted by batch size (the Keras loss metric), accumulated on the device
+        and read once per epoch."""
+        from . import optimizers as _opt
+        from .metrics import _device_f32
+        try:
+            optimizer = _opt.resolve(self.optimizer)
+        except ValueError as e:
+            raise ValueError(f"fit_head: {e}") from None
+        if int(epochs) < 0:
+            raise ValueError(f"fit_head: epochs must be >= 0, got {epochs}")
+        if encoded is not None:
+            if y is None:
+                raise ValueError("fit_head: encoded= needs the labels in y")
+            batches = list(self._evaluate_batches(encoded, y, batch_size))
+            features = [b[0] for b in batches]
+        else:
+            batches = None
+            features = {}
+        hist = _opt.History()
+        with torch.cuda.device(self.device):
+            running = torch.zeros(2, dtype=torch.float64, device=self.device)
+            for epoch in range(int(epochs)):
+                if lr_schedule is not None:
+                    optimizer.learning_rate = float(lr_schedule(epoch, optimizer.learning_rate))
+                running.zero_()
+                source = batches if batches is not None else self._evaluate_batches(x, y, batch_size)
+                for i, (images, labels) in enumerate(source):
+                    n = len(labels)
+                    if n == 0:
+                        continue
+                    if batches is not None:
+                        feats = features[i]
+                    elif cache_features:
+                        if i not in features:
+                            features[i] = self.encode(images)
+                        feats = features[i]
+                    else:
+                        feats = None
+                    out5 = self.train_head_on_batch(images, _device_f32(labels, self.device),
+                                                    encoded=feats)
+                    running[0] += out5[0].double() * n
+                    running[1] += n
+                total, count = running.cpu().tolist()       # the epoch's one host read
+                hist.history["loss"].append(total / count if count else float("nan"))
+                hist.epoch.append(epoch)
+        return hist
+
+    def _head_pass(self, what, images, y_true, encoded, weight_grads=None):
+        """The part head_gradients and train_head_on_batch share: the checks, the encoder
+        features, the training forward for the logits, the loss gradient there, and the
+        backward.  `weight_grads`: buffers to write the weight gradients into (the optimizer's
+        persistent ones; d loss / d encoded_images is then not computed); None allocates them
+        and the encoded_images gradient.  Returns (out5, grads)."""
+        if self.dtype not in (L.BF16X3, L.BF16):
+            raise ValueError(f"{what}: the head backward runs in the 'bf16x3' and "
                              "'bfloat16' modes only (not float32 / float8)")
         from . import loss as _loss
         params = _loss.fused_loss_params(self.loss) if self.loss is not None else None
         if params is None:
-            raise ValueError("head_gradients: compile(loss=my_custom_loss or a functools.partial "
+            raise ValueError(f"{what}: compile(loss=my_custom_loss or a functools.partial "
                              "of it with keyword arguments) first")
         dims = self.dims
         with torch.cuda.device(self.device):
@@ -612,7 +731,7 @@ class Model:
                 encoded = torch.as_tensor(encoded).to(device=self.device,
                                                       dtype=torch.float32).contiguous()
                 if encoded.dim() != 3 or tuple(encoded.shape[1:]) != (dims.tokens, dims.d):
-                    raise ValueError(f"head_gradients: encoded must be (B, {dims.tokens}, "
+                    raise ValueError(f"{what}: encoded must be (B, {dims.tokens}, "
                                      f"{dims.d}), got {tuple(encoded.shape)}")
             b = encoded.shape[0]
             cfg = self.config(b)
@@ -622,8 +741,11 @@ class Model:
             if getattr(self, "_hb_ws", None) is None or self._hb_ws.numel() < need.value:
                 self._hb_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
             wdev = self._head_master()
-            grads = OrderedDict((n, torch.empty_like(t)) for n, t in wdev.items())
-            grads["encoded_images"] = torch.empty_like(encoded)
+            if weight_grads is None:
+                grads = OrderedDict((n, torch.empty_like(t)) for n, t in wdev.items())
+                grads["encoded_images"] = torch.empty_like(encoded)
+            else:
+                grads = weight_grads
             P, G = L.VtdHeadParams(), L.VtdHeadGrads()
             for S, src in ((P, wdev), (G, grads)):
                 S.w_det, S.b_det = src["dense/kernel"].data_ptr(), src["dense/bias"].data_ptr()
@@ -632,7 +754,7 @@ class Model:
                     S.b_head[j] = src[f"dense_{j + 1}/bias"].data_ptr()
                 S.w_final = src["MLP_Head_no_Sigmoid/kernel"].data_ptr()
                 S.b_final = src["MLP_Head_no_Sigmoid/bias"].data_ptr()
-            G.d_encoded = grads["encoded_images"].data_ptr()
+            G.d_encoded = L.ptr(grads.get("encoded_images"))
             st = L.stream_ptr()
             # the training forward alone for its logits, the loss gradient at those logits,
             # then the forward again with the backward
@@ -677,7 +799,7 @@ def create_vision_transformer_detector(
     [0, 1) builds the same forward and the same weight names; only a build-time
     `training=True` (dropout forced on in every call) is refused.  `max_weight`/`clip_weight` are weight constraints
     Keras applies only after optimizer steps (vtd.py:209-236), so they do not affect
-    the forward and are accepted as no-ops.  Extra keyword-only options: `dtype`, `device`,
+    the forward; train_head_on_batch / fit_head apply them after every step.  Extra keyword-only options: `dtype`, `device`,
     `seed`.  `dtype` defaults to 'bf16x3', the split-bf16 parity mode: every product as three
     bf16 MFMA products with fp32 accumulation and fp32 softmax / LayerNorm statistics, within
     1e-4 of the fp32 reference's logits (measured 1.6e-5 at C2) -- so a caller that swaps the
