@@ -354,7 +354,11 @@ int vtd_resize_with_pad(const uint8_t* pixels_dev, const int64_t* offsets_dev,
  * Huffman JPEG: 8-bit, 1, 3 or 4 (CMYK / YCCK) components, 4:4:4 / 4:2:2 / 4:2:0, restart
  * intervals.  libjpeg-turbo's decode path (what TF uses): ISLOW IDCT, fancy upsampling,
  * YCbCr -> RGB; gray -> RGB replicated; CMYK (YCCK -> CMYK as jdcolor.c) -> RGB as TF's
- * jpeg_mem.cc (Adobe marker: R = K C / 255, else (255 - K)(255 - C) / 255).  Other JPEGs
+ * jpeg_mem.cc (Adobe marker: R = K C / 255, else (255 - K)(255 - C) / 255).  The colour space
+ * of a 3-component file is libjpeg's choice (jdapimin.c default_decompress_parms), in this
+ * order: a JFIF APP0 marker means YCbCr; otherwise an Adobe APP14 marker decides (transform 0:
+ * RGB, else YCbCr); otherwise the component ids do ('R' 'G' 'B': RGB, all others YCbCr).  Both
+ * markers count only before the first scan.  Other JPEGs
  * (arithmetic-coded, lossless, 12-bit, 4:4:0, ...) return VTD_ERR_UNSUPPORTED with the reason.
  * vtd_jpeg_info: header only (host).  The images are HOST buffers; their marker segments are
  * parsed on the host, the entropy-coded data + derived tables copied to the workspace on

@@ -10,8 +10,11 @@
 //   - jdsample.c h2v1 / h2v2 fancy upsampling (triangle filter; plain replication when the
 //     downsampled width is <= 2), context rows replicated at the top / bottom edge as
 //     jdmainct.c does;
-//   - jdcolor.c ycc_rgb_convert (16-bit fixed-point tables), gray -> RGB replication.
-// Parity: bit-exact against libjpeg-turbo as bundled with Pillow (tests/test_gpu_jpeg.py).
+//   - jdcolor.c ycc_rgb_convert (16-bit fixed-point tables), gray -> RGB replication; whether
+//     three components are YCbCr or RGB as jdapimin.c default_decompress_parms decides (JFIF,
+//     then the Adobe transform, then the component ids).
+// Parity: bit-exact against libjpeg-turbo as bundled with Pillow (tests/test_gpu_jpeg.py on
+// Pillow-written files, tests/test_gpu_jpeg_streams.py on hand-built ones).
 //
 // Split of work: the marker segments are parsed on the host (a few hundred bytes per image:
 // tables, frame and scan headers); the entropy-coded data and the derived Huffman / quant
@@ -55,7 +58,7 @@ struct JpegComp {
 };
 
 struct JpegDesc {
-  int h, w, nc, mcux, mcuy, hmax, vmax, restart, rgb;   // rgb: Adobe transform 0 (no YCC)
+  int h, w, nc, mcux, mcuy, hmax, vmax, restart, rgb;   // rgb: 3 components coded as RGB
   int adobe;                // an Adobe APP14 marker was seen (CMYK polarity, see pixel_rgb)
   int ycck;                 // 4 components coded as YCCK (Adobe transform != 0)
   int nblocks;              // blocks of all components
@@ -200,7 +203,8 @@ bool parse_jpeg(const uint8_t* b, size_t n, JpegDesc& d, size_t& seg, size_t& se
   if (scans) scans->clear();
   if (n < 4 || b[0] != 0xFF || b[1] != 0xD8) { err = "jpeg: no SOI marker"; return false; }
   RawHuff huff[8];
-  bool qdef[4] = {}, frame = false;
+  bool qdef[4] = {}, frame = false, jfif = false;
+  int adobe_transform = -1;                 // of an Adobe marker before the first scan
   // libjpeg-turbo latches a component's quantization table at the component's first scan
   // (jdinput.c latch_quant_tables); a progressive file redefining a latched table with other
   // values afterwards would need per-component copies: refused
@@ -322,12 +326,15 @@ bool parse_jpeg(const uint8_t* b, size_t n, JpegDesc& d, size_t& seg, size_t& se
     } else if (m == 0xDD) {                                   // DRI
       if (len < 4) { err = "jpeg: truncated DRI segment"; return false; }
       d.restart = u16(s);
+    } else if (m == 0xE0 && len >= 16 && nscans == 0 && !memcmp(b + s, "JFIF\0", 5)) {
+      jfif = true;                                            // jdmarker.c examine_app0
     } else if (m == 0xEE && len >= 14 && !memcmp(b + s, "Adobe", 5)) {
-      // jdmarker.c get_interesting_appn / jdapimin.c default_decompress_parms: transform 0
-      // = RGB (3 components) / CMYK (4); otherwise YCbCr / YCCK
+      // jdmarker.c examine_app14: four components are CMYK (transform 0) or YCCK; for three
+      // the colour space follows below, from the markers before the first scan, where
+      // libjpeg chooses it
       d.adobe = 1;
-      d.rgb = b[s + 11] == 0 ? 1 : 0;
       d.ycck = b[s + 11] != 0 ? 1 : 0;
+      if (nscans == 0) adobe_transform = b[s + 11];
     } else if (m == 0xDA) {                                   // SOS
       if (!frame) { err = "jpeg: scan before frame"; return false; }
       if (len < 3) { err = "jpeg: truncated SOS segment"; return false; }
@@ -418,6 +425,17 @@ bool parse_jpeg(const uint8_t* b, size_t n, JpegDesc& d, size_t& seg, size_t& se
       continue;
     }
     pos = e;
+  }
+  // jdapimin.c default_decompress_parms, three components: a JFIF marker means YCbCr;
+  // otherwise an Adobe marker decides (transform 0: RGB, anything else YCbCr); otherwise the
+  // component ids do ('R' 'G' 'B': RGB; 1 2 3 and everything else: YCbCr)
+  if (d.nc == 3) {
+    if (jfif)
+      d.rgb = 0;
+    else if (adobe_transform >= 0)
+      d.rgb = adobe_transform == 0 ? 1 : 0;
+    else
+      d.rgb = d.comp[0].id == 'R' && d.comp[1].id == 'G' && d.comp[2].id == 'B' ? 1 : 0;
   }
   for (int c = 0; c < d.nc; ++c)
     if (!qdef[d.comp[c].tq]) { err = "jpeg: missing quantization table"; return false; }
