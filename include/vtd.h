@@ -638,6 +638,50 @@ int vtd_head_backward(const vtd_config* cfg, const vtd_head_params* w, const flo
                       const float* dlogits_dev, float* logits_dev, const vtd_head_grads* g,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* ---- attention backward (VTD_BF16 / VTD_BF16X3; any other dtype VTD_ERR_UNSUPPORTED)
+ * vtd_attention_train: vtd_attention that also writes lse_dev, fp32 [B][heads][N]:
+ * lse[b][h][i] = ln sum_j exp(scale q_i.k_j), natural units, finite whenever the scores are.
+ * It runs the streaming kernels of vtd_attention (VTD_BF16X3 at the default; VTD_BF16 as
+ * under VTD_KNOB_ATTN_VARIANT 2) with the LSE store compiled in: out_dev has the same bits. */
+int vtd_attention_train(const void* qkv_dev, int B, int N, int heads, int dkp, int ldqkv,
+                        float scale, void* out_dev, int ldo, float* lse_dev, int dtype,
+                        void* stream);
+/* dqkv = d loss / d qkv of the attention core from do_dev = d loss / d O.
+ *   qkv_dev  as the forward read it: bf16 (VTD_BF16) or fp32 (VTD_BF16X3), [B*N][ldqkv];
+ *   o_dev    as the forward wrote it: bf16 [B*N][ldo], or the split [hi | lo] operand (piece
+ *            width ldo / 2);
+ *   do_dev   bf16 (VTD_BF16) or fp32 (VTD_BF16X3) [B*N][lddo], head h at column h*dkp.  The
+ *            pad columns [key_dim, dkp) of a head are READ: the caller keeps them zero (they
+ *            are after the attention-output input-gradient GEMM, whose packed w_out has zero
+ *            rows there), as the pad columns of qkv are everywhere in this library;
+ *   lse_dev  from vtd_attention_train on the same qkv and scale.
+ * dqkv_dev has qkv's column layout and is written in `dtype` form exactly as vtd_act_grad
+ * writes gz: bf16 rows (lddqkv % 8 == 0), or split [hi | lo] with piece width lddqkv / 2
+ * (lddqkv % 16 == 0), 16-byte aligned -- directly the A operand of the qkv input-gradient GEMM
+ * and the G operand of vtd_gemm_wgrad.  For rows < B*N the columns [0, 3 heads dkp) of each
+ * piece are written in full (pad columns of a head come out zero); nothing else is written.
+ * P = exp(scale q.k - lse) is recomputed, never stored as N x N:
+ *   delta_i = sum_d dO_id O_id, dP = dO V^T, dS = P o (dP - delta) scale,
+ *   dV = P^T dO, dK = dS^T Q, dQ = dS K,
+ * each product one bf16 MFMA product (VTD_BF16) or the three hi.hi + lo.hi + hi.lo
+ * (VTD_BF16X3; P and dS split as the forward splits P), fp32 accumulation and statistics.
+ * No atomics and no workgroup waiting on another: dK, dV come from a key-stationary pass, dQ
+ * from a second, query-stationary pass; bit-identical from run to run.  VTD_BF16X3 divides the
+ * recomputed P by its own row sums (one more sweep of the keys), so the rounding of lse, one
+ * fp32 number per row, does not reach the gradients.  Nothing is read past row B*N - 1.  Within 2e-4 (VTD_BF16X3) / 5e-2 (VTD_BF16) of max |gradient| per tensor
+ * against fp64 (tests/test_gpu_attention_backward.py).
+ * ld rules: ldqkv, lddo multiples of 8 (>= 3 heads dkp, >= heads dkp); ldo as vtd_attention
+ * writes it; every base 16-byte aligned; scale positive and finite; else VTD_ERR_INVALID_ARG,
+ * before any device call.  ws_bytes >= vtd_attention_backward_workspace_bytes (delta, and in
+ * VTD_BF16X3 the reciprocal row sums: fp32 [B][heads][N] each), else VTD_ERR_WORKSPACE.  Asynchronous on `stream`, no allocation, no host
+ * synchronisation. */
+int vtd_attention_backward_workspace_bytes(int B, int N, int heads, int dkp, int dtype,
+                                           size_t* bytes);
+int vtd_attention_backward(const void* qkv_dev, const void* o_dev, const void* do_dev,
+                           const float* lse_dev, int B, int N, int heads, int dkp, int ldqkv,
+                           int ldo, int lddo, float scale, void* dqkv_dev, int lddqkv, int dtype,
+                           void* ws_dev, size_t ws_bytes, void* stream);
+
 /* ---- optimizer step: keras.optimizers.Adam + the ClipWeight constraint + the operand re-pack
  * One tensor of the table: w, m, v (updated in place) and g (read only), fp32 device arrays
  * in the Keras layout with 16-B aligned bases.  VTD_ADAM_MATRIX: a kernel [K][N] row-major;

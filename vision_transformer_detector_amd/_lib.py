@@ -198,7 +198,14 @@ SIGNATURES = {
     "vtd_head_backward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdHeadParams),
                                   c_void_p, c_void_p, c_void_p, ctypes.POINTER(VtdHeadGrads),
                                   c_void_p, c_size_t, c_void_p]),
-    "vtd_adam_plan_bytes": (c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int,
+    "vtd_attention_train": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                    c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "vtd_attention_backward_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int,
+                                                       ctypes.POINTER(c_size_t)]),
+    "vtd_attention_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                       c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "vtd_adam_plan_bytes":(c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int,
                                     ctypes.POINTER(c_size_t), ctypes.POINTER(c_int)]),
     "vtd_adam_plan_upload": (c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int, c_void_p,
                                      c_size_t, c_void_p]),

@@ -266,11 +266,13 @@ struct AttnBf16Cfg {
 // XCD-aware (xcd_remap != 0): blocks b, b + 8, ... share an XCD and walk one contiguous range
 // of (pair, query block) ids, so a pair's query blocks run on one XCD and read its K / V
 // through that XCD's L2 once instead of once per XCD from beyond it.
-template <int DKP, int NWG, bool MX8 = false>
+// LSE (vtd_attention_train): the same kernel also writes lse[b][h][q] = ln sum_k exp(score),
+// natural units, from the statistics it already holds; O is computed by the same instructions.
+template <int DKP, int NWG, bool MX8 = false, bool LSE = false>
 __global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void attention_bf16_kernel(
     const bf16_t* __restrict__ qkv, int N, int heads, int ldqkv, float scale_log2,
     bf16_t* __restrict__ out, int ldo, uint8_t* __restrict__ s8, int64_t s_rows, int nqb,
-    int xcd_remap) {
+    int xcd_remap, float* __restrict__ lse = nullptr) {
   using C = AttnBf16Cfg<DKP>;
   typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -534,8 +536,15 @@ __global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void
   chunk(nchunks - 1, std::true_type{});
   if (!active) return;
   // osum rows hold the whole key sum (both lane halves' keys); l_run holds this half's
-  const float inv = 1.f / (SUMMFMA ? osum[0] : pair_sum(l_run));
+  const float l_all = SUMMFMA ? osum[0] : pair_sum(l_run);
+  const float inv = 1.f / l_all;
   const int q = q0 + col;
+  if constexpr (LSE) {
+    // the max in use is m_run + m_res (log2 units); both lane halves hold the same statistics
+    if (half == 0 && q < N)
+      lse[((int64_t)b * heads + h) * N + q] =
+          (m_run + m_res + __builtin_amdgcn_logf(l_all)) * 0.6931471805599453f;
+  }
   if constexpr (!MX8 && DKP == 64) {
     // bf16 output through LDS (free after the loop's last barrier): a lane holds 16-B
     // pieces of one query row spread over 8 columns groups, so direct stores write 16 B
@@ -1453,10 +1462,10 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& h
                                         (int)pack_lo_bf16x2(b[2], b[3], h3)});
 }
 
-template <int DKP, int NWG, int KC = 64, int MINB = 1>
+template <int DKP, int NWG, int KC = 64, int MINB = 1, bool LSE = false>
 __global__ __launch_bounds__(64 * NWG, MINB) void attention_x3_kernel(
     const float* __restrict__ qkv, int N, int heads, int ldqkv, float scale_log2,
-    bf16_t* __restrict__ out, int ldo, int nqb) {
+    bf16_t* __restrict__ out, int ldo, int nqb, float* __restrict__ lse = nullptr) {
   using C = AttnX3Cfg<DKP, KC>;
   typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1637,7 +1646,13 @@ __global__ __launch_bounds__(64 * NWG, MINB) void attention_x3_kernel(
   for (int c = 0; c + 1 < nchunks; ++c) chunk(c, std::false_type{});
   chunk(nchunks - 1, std::true_type{});
   if (!active) return;
-  const float inv = 1.f / pair_sum(l_run);
+  const float l_all = pair_sum(l_run);
+  const float inv = 1.f / l_all;
+  if constexpr (LSE) {
+    if (half == 0 && q0 + col < N)
+      lse[((int64_t)b * heads + h) * N + q0 + col] =
+          (m_run + __builtin_amdgcn_logf(l_all)) * 0.6931471805599453f;
+  }
   if constexpr (DKP == 64) {
     // restaged through the LDS free after the loop's last barrier: per wave a hi and a lo
     // image of its 32 query rows (row stride 144 B), then whole 128-B rows per store
@@ -1685,9 +1700,9 @@ __global__ __launch_bounds__(64 * NWG, MINB) void attention_x3_kernel(
     }
 }
 
-template <int DKP, int KC = 64, int MINB = 1>
+template <int DKP, int KC = 64, int MINB = 1, bool LSE = false>
 int launch_x3(const void* qkv, int B, int N, int heads, int ldqkv, float scale, void* out,
-              int ldo, hipStream_t stream) {
+              int ldo, hipStream_t stream, float* lse = nullptr) {
   using C = AttnX3Cfg<DKP, KC>;
   constexpr int NWG = 8;
   // the K / V double buffer, or (dkp 64) the output restage: a hi and a lo image of 32 rows
@@ -1697,20 +1712,20 @@ int launch_x3(const void* qkv, int B, int N, int heads, int ldqkv, float scale, 
   VTD_CHECK_ARG((int64_t)nqb * heads * B < INT32_MAX, "attention: grid too large");
   static std::once_flag once[kMaxDevices];
   once_per_device(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_x3_kernel<DKP, NWG, KC, MINB>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_x3_kernel<DKP, NWG, KC, MINB, LSE>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
   });
-  hipLaunchKernelGGL((attention_x3_kernel<DKP, NWG, KC, MINB>), dim3(nqb * heads * B),
+  hipLaunchKernelGGL((attention_x3_kernel<DKP, NWG, KC, MINB, LSE>), dim3(nqb * heads * B),
                      dim3(64 * NWG), LDS, stream, static_cast<const float*>(qkv), N, heads, ldqkv,
-                     scale * 1.4426950408889634f, static_cast<bf16_t*>(out), ldo, nqb);
+                     scale * 1.4426950408889634f, static_cast<bf16_t*>(out), ldo, nqb, lse);
   VTD_LAUNCH_CHECK("attention_x3");
   return VTD_OK;
 }
 
-template <int DKP, int NWG, bool MX8 = false>
+template <int DKP, int NWG, bool MX8 = false, bool LSE = false>
 int launch_bf16_v2(const void* qkv, int B, int N, int heads, int ldqkv, float scale,
                    void* out, int ldo, hipStream_t stream, uint8_t* s8 = nullptr,
-                   int64_t s_rows = 0) {
+                   int64_t s_rows = 0, float* lse = nullptr) {
   using C = AttnBf16Cfg<DKP>;
   const int nq = (N + 31) / 32, nqb = (nq + NWG - 1) / NWG;
   VTD_CHECK_ARG((int64_t)nqb * heads * B < INT32_MAX, "attention: grid too large");
@@ -1718,17 +1733,17 @@ int launch_bf16_v2(const void* qkv, int B, int N, int heads, int ldqkv, float sc
   static std::once_flag once[kMaxDevices];
   once_per_device(once, [] {
     (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&attention_bf16_kernel<DKP, NWG, MX8>),
+        reinterpret_cast<const void*>(&attention_bf16_kernel<DKP, NWG, MX8, LSE>),
         hipFuncAttributeMaxDynamicSharedMemorySize, 2 * C::BUF);
   });
   // XCD-aware order: C3 attention 382.5-383.2 vs 384.0-384.2 us per launch, forward
   // 1,812-1,813 vs 1,783-1,790 img/s (profiles/r03_attn_xcd_order_ab.log); the kernel is
   // VALU-bound, its K / V re-reads were mostly served beyond L2 at no visible cost
   const int xcd_remap = 1;
-  hipLaunchKernelGGL((attention_bf16_kernel<DKP, NWG, MX8>), grid, dim3(64 * NWG), 2 * C::BUF,
+  hipLaunchKernelGGL((attention_bf16_kernel<DKP, NWG, MX8, LSE>), grid, dim3(64 * NWG), 2 * C::BUF,
                      stream, static_cast<const bf16_t*>(qkv), N, heads, ldqkv,
                      scale * 1.4426950408889634f, static_cast<bf16_t*>(out), ldo, s8, s_rows,
-                     nqb, xcd_remap);
+                     nqb, xcd_remap, lse);
   VTD_LAUNCH_CHECK("attention_bf16");
   return VTD_OK;
 }
@@ -1827,6 +1842,48 @@ int attention_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqk
   return launch<float, 128>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream);
 }
 
+// vtd_attention_train: the streaming kernels vtd_attention runs (VTD_BF16X3 at the default;
+// VTD_BF16 as under VTD_KNOB_ATTN_VARIANT 2: 4 waves up to N = 128, else 8), instantiated with
+// LSE, so O has the same bits and lse comes from the same statistics.
+int attention_train_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
+                           float scale, void* out, int ldo, float* lse, int dtype,
+                           hipStream_t stream) {
+  VTD_CHECK_ARG(qkv && out && lse, "attention_train: null pointer");
+  VTD_CHECK_ARG(B > 0 && N > 0 && heads > 0, "attention_train: bad B/N/heads");
+  VTD_CHECK_ARG(dkp == 32 || dkp == 64 || dkp == 128, "attention_train: dkp must be 32/64/128");
+  VTD_CHECK_ARG(scale > 0 && std::isfinite(scale),
+                "attention_train: scale must be positive and finite");
+  if (dtype != VTD_BF16 && dtype != VTD_BF16X3)
+    return fail(VTD_ERR_UNSUPPORTED, "attention_train: dtype must be VTD_BF16 or VTD_BF16X3");
+  const bool x3 = dtype == VTD_BF16X3;
+  VTD_CHECK_ARG(!x3 || ldo % 2 == 0, "attention_train: a split-bf16 output needs ldo % 2 == 0");
+  const int owidth = x3 ? ldo / 2 : ldo;
+  VTD_CHECK_ARG(ldqkv >= 3 * heads * dkp && owidth >= heads * dkp,
+                "attention_train: leading dimensions too small");
+  VTD_CHECK_ARG(ldqkv % 8 == 0 && owidth % 8 == 0, "attention_train: ld must be multiple of 8");
+  ProfScope ps(stream, PROF_ATTN, 4.0 * B * heads * (double)N * N * dkp);
+  if (x3) {
+    if (dkp == 32)
+      return launch_x3<32, 64, 1, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse);
+    if (dkp == 64 && knob(VTD_KNOB_ATTN_VARIANT) != 10)
+      return launch_x3<64, 32, 2, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse);
+    if (dkp == 64)
+      return launch_x3<64, 64, 1, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse);
+    return launch_x3<128, 64, 1, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse);
+  }
+#define VTD_TRAIN_BF16(D, W) \
+  launch_bf16_v2<D, W, false, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, nullptr, 0, lse)
+  if (N > 128) {
+    if (dkp == 32) return VTD_TRAIN_BF16(32, 8);
+    if (dkp == 64) return VTD_TRAIN_BF16(64, 8);
+    return VTD_TRAIN_BF16(128, 8);
+  }
+  if (dkp == 32) return VTD_TRAIN_BF16(32, 4);
+  if (dkp == 64) return VTD_TRAIN_BF16(64, 4);
+  return VTD_TRAIN_BF16(128, 4);
+#undef VTD_TRAIN_BF16
+}
+
 int attention_mx8_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
                          float scale, uint8_t* q, int ldq, uint8_t* s, int64_t s_rows,
                          hipStream_t stream, double flops) {
@@ -1872,4 +1929,11 @@ extern "C" int vtd_attention(const void* qkv_dev, int B, int N, int heads, int d
                              void* stream) {
   return vtd::attention_launch(qkv_dev, B, N, heads, dkp, ldqkv, scale, out_dev, ldo,
                                dtype, static_cast<hipStream_t>(stream), 0.0, 1);
+}
+
+extern "C" int vtd_attention_train(const void* qkv_dev, int B, int N, int heads, int dkp,
+                                   int ldqkv, float scale, void* out_dev, int ldo,
+                                   float* lse_dev, int dtype, void* stream) {
+  return vtd::attention_train_launch(qkv_dev, B, N, heads, dkp, ldqkv, scale, out_dev, ldo,
+                                     lse_dev, dtype, static_cast<hipStream_t>(stream));
 }

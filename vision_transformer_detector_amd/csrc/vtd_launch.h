@@ -42,6 +42,17 @@ int attention_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqk
 int attention_mx8_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
                          float scale, uint8_t* q, int ldq, uint8_t* s, int64_t s_rows,
                          hipStream_t stream, double flops);
+int attention_train_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
+                           float scale, void* out, int ldo, float* lse, int dtype,
+                           hipStream_t stream);
+
+// ----------------------------------------------------------------- vtd_attention_bwd.hip
+int attention_backward_workspace_bytes(int B, int N, int heads, int dkp, int dtype,
+                                       size_t* bytes);
+int attention_backward_launch(const void* qkv, const void* o, const void* dO, const float* lse,
+                              int B, int N, int heads, int dkp, int ldqkv, int ldo, int lddo,
+                              float scale, void* dqkv, int lddqkv, int dtype, void* ws,
+                              size_t ws_bytes, hipStream_t stream);
 
 // ----------------------------------------------------------------- vtd_elementwise.hip
 int layernorm_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx, const float* g,
