@@ -8,7 +8,9 @@ arithmetic, in the reference's operation order, so the HIP metric kernels
 Parity PINNED: the 12 known-answer tests of
 testcases_vision_transformer_detector.py:11-734 (AP = 1, 1, 0.3, 0, 0, 0.75, 0, 1, 0.375,
 0.5, 0.5, 0.6875, and the reset state) are restated in tests/test_map_kat.py and must hold
-for this module and for the GPU path.
+for this module and for the GPU path.  None of those has three objects of one class: the sort,
+cut and 14-hit branches are pinned by four cases of tests/map_designs.py derived by hand from
+the reference's text (DESIGNED_KAT in tests/test_map_kat.py).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may import this module.
 

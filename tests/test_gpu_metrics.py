@@ -1,13 +1,16 @@
 """Device metric (vtd_map_update / vtd_map_result / vtd_iou) against the reference's
 known answers (testcases_vision_transformer_detector.py:11-734) and, bit for bit, against
-the float32 CPU restatement (oracle/vtd_map.py) on seeded random batches."""
+the float32 CPU restatement (oracle/vtd_map.py) on seeded random batches and on the designed
+cases of tests/map_designs.py, which reach the branches the random batches never do."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import vtd_map as M
 from oracle import vtd_numpy as V
+from tests import map_designs as D
 from tests.map_cases import CASES, random_batch
+from tests.test_map_kat import DESIGNED_KAT, check_designed_kat
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +44,8 @@ def test_map_reset_state(vtd, cuda):
 
 
 def _compare_state(m, ref):
-    np.testing.assert_array_equal(m.latest_positive_bboxes.cpu().numpy(), ref.latest_positive_bboxes)
+    np.testing.assert_array_equal(m.latest_positive_bboxes.cpu().numpy(),
+                                  ref.latest_positive_bboxes)
     np.testing.assert_array_equal(m.labels_quantity_per_image.cpu().numpy(),
                                   ref.labels_quantity_per_image)
     np.testing.assert_array_equal(m.showed_up_classes.cpu().numpy(), ref.showed_up_classes)
@@ -50,8 +54,12 @@ def _compare_state(m, ref):
 @pytest.mark.parametrize("seed,classes", [(0, (0, 80)), (1, (0, 3)), (2, (77, 80)), (3, (0, 1))])
 def test_map_random_batches_match_oracle(vtd, cuda, seed, classes):
     """Several batch updates (ragged object counts, duplicate predictions, classes near
-    the rounding boundary, >14 boxes of one class so the sort/truncate branches run):
-    the whole state and every per-threshold AP must equal the restatement exactly."""
+    the rounding boundary): the whole state and every per-threshold AP must equal the
+    restatement exactly.  What this covers, counted by tests/map_designs.fuzz_replay: scenarios
+    b and c with fewer than 14 predictions, greedy matching with at most 7 hits, ties at the
+    maximum IoU, and left-overs that fit.  At most 9 positive predictions of one class meet in
+    an image, so no sort or cut runs, nor the 14-hit exit, nor two labels of equal area: those
+    are test_map_designed_cases below."""
     rng = np.random.default_rng(seed)
     m, ref = vtd.MeanAveragePrecision(), M.MeanAveragePrecision()
     for step, batch in enumerate((5, 1, 9)):
@@ -74,6 +82,25 @@ def test_map_batch_larger_than_block(vtd, cuda):
     ref.update_state(y, p)
     _compare_state(m, ref)
     assert m.result().item() == ref.result()
+
+
+@pytest.mark.parametrize("name", sorted(D.CASES))
+def test_map_designed_cases(vtd, cuda, name):
+    """tests/map_designs.py: after every update_state the three state arrays equal the
+    restatement's, as do the per-threshold APs and the mAP as float32; the four hand-derived
+    cases also meet the literals of tests/test_map_kat.py."""
+    m, ref = vtd.MeanAveragePrecision(), M.MeanAveragePrecision()
+    for y, p in D.CASES[name]()[0]:
+        m.update_state(y, p, use_transform_predictions=False)
+        ref.update_state(y, p)
+        _compare_state(m, ref)
+        got = m.average_precision_per_iou().cpu().numpy()
+        assert got.dtype == np.float32
+        np.testing.assert_array_equal(got, np.array(ref.per_iou(), np.float32))
+        assert np.float32(m.result().item()) == ref.result()
+    if name in DESIGNED_KAT:
+        check_designed_kat(name, m.latest_positive_bboxes[79, 0].cpu().numpy(),
+                           m.labels_quantity_per_image[79, 0].item(), got)
 
 
 def test_map_update_from_logits(vtd, cuda):
@@ -115,3 +142,26 @@ def test_iou_calculator_matches_oracle(vtd, cuda):
     p[1, 2:] = (9.5, 9.5, 7, 7)
     got = vtd.iou_calculator(torch.from_numpy(y).cuda(), torch.from_numpy(p).cuda()).cpu().numpy()
     assert abs(got[0] - 0.64) < 1e-6 and abs(got[1] - 0.49) < 1e-6
+
+
+def test_iou_designed_pairs(vtd, cuda):
+    """Boxes that touch along an edge or at a corner (the overlap test is strict: IoU 0),
+    identical boxes, an overlap of one float32 step, containment, a zero-height box, two
+    zero-size boxes at one point, a removed (-8) row: bit for bit, and the first three also
+    as literals."""
+    lab, pred = D.iou_operands(len(D.IOU_PAIRS), 4)
+    got = vtd.iou_calculator(lab, pred).cpu().numpy()
+    np.testing.assert_array_equal(got, M.iou_calculator(lab, pred))
+    for (name, _, _, literal), v in zip(D.IOU_PAIRS, got):
+        assert literal is None or v == np.float32(literal), (name, v)
+    assert got[[q[0] for q in D.IOU_PAIRS].index("overlap_one_ulp")] > 0
+
+
+@pytest.mark.parametrize("n,stride", [(1, 4), (257, 4), (257, 6), (4096 * 256 + 5, 4)])
+def test_iou_sizes_and_strides(vtd, cuda, n, stride):
+    """One row, one row past a block, 6-channel rows (boxes in the last 4), and 5 rows past
+    the 4096 x 256 threads the launch is capped at: the grid-stride loop's second trip."""
+    lab, pred = D.iou_operands(n, stride)
+    got = vtd.iou_calculator(lab, pred).cpu().numpy()
+    assert got.shape == (n,)
+    np.testing.assert_array_equal(got, M.iou_calculator(lab, pred))
