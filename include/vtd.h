@@ -682,6 +682,41 @@ int vtd_attention_backward(const void* qkv_dev, const void* o_dev, const void* d
                            int ldo, int lddo, float scale, void* dqkv_dev, int lddqkv, int dtype,
                            void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---- LayerNorm backward (an addition to ABI 17; DESIGN.md "Encoder block backward")
+ * The gradients of keras LayerNormalization(axis=-1) given d loss / d y, all fp32 (in training
+ * the residual stream and its gradient are fp32 in every operand mode, so there is no dtype):
+ *   xhat = (x - mean) rstd, gy = dy gamma,
+ *   dx = rstd ((gy - mean_D(gy)) - xhat mean_D(gy xhat)) [+ add],
+ *   dgamma = sum_rows dy xhat, dbeta = sum_rows dy.
+ * x_dev [rows][ldx]: the forward's input rows; stat_dev: (mean, rstd) per row as
+ * vtd_layernorm_stats writes them, 8-byte aligned; gamma_dev [D]; dy_dev [rows][lddy];
+ * add_dev [rows][ldadd] (nullable): the gradient that reaches the same tensor along the
+ * residual connection, added to dx in the same pass; dx_dev [rows][lddx] may be the very buffer
+ * add_dev is (same base, same leading dimension) and overlaps no other argument.  dgamma_dev,
+ * dbeta_dev [D]: both or neither; without them no workspace is needed (ws_dev may be NULL).
+ * Nothing is read in rows >= `rows` or columns >= D; exactly the rows x D elements of dx and
+ * the D elements of dgamma and of dbeta are written, so pad columns up to lddx keep their
+ * bytes.  Every operation rounds once in fp32 (no FMA contraction); the row means are summed
+ * per lane in column order and across the wave as the forward's statistics are.
+ * dgamma / dbeta use no atomics and no workgroup waits on another: the rows are cut into
+ * vtd_layernorm_backward_workspace_bytes / (8 D) contiguous ranges -- a function of `rows`
+ * alone, never of the device -- each range's sums are written as one fp32 [2][D] plane of the
+ * workspace and a second kernel adds the planes in range order: the same inputs give the same
+ * bits on every run.  Rows with 16-byte aligned x / gamma / dy / add / dx, D % 4 == 0, D <= 4096
+ * and leading dimensions that are multiples of 4 take the vector kernels; anything else a
+ * generic path with the same summation order for dgamma / dbeta.
+ * VTD_ERR_INVALID_ARG before any device call: a null x / stat / gamma / dy / dx (or workspace
+ * when dgamma is given), a non-positive size, a leading dimension below D, dgamma without
+ * dbeta or the reverse, stat not 8-byte, another pointer not 4-byte or the workspace not
+ * 16-byte aligned.  ws_bytes below vtd_layernorm_backward_workspace_bytes (with dgamma given):
+ * VTD_ERR_WORKSPACE.  Asynchronous on `stream`, no allocation, no host synchronisation. */
+int vtd_layernorm_backward_workspace_bytes(int64_t rows, int D, size_t* bytes);
+int vtd_layernorm_backward(const float* x_dev, int ldx, const float* stat_dev,
+                           const float* gamma_dev, const float* dy_dev, int lddy,
+                           const float* add_dev, int ldadd, int64_t rows, int D, float* dx_dev,
+                           int lddx, float* dgamma_dev, float* dbeta_dev, void* ws_dev,
+                           size_t ws_bytes, void* stream);
+
 /* ---- optimizer step: keras.optimizers.Adam + the ClipWeight constraint + the operand re-pack
  * One tensor of the table: w, m, v (updated in place) and g (read only), fp32 device arrays
  * in the Keras layout with 16-B aligned bases.  VTD_ADAM_MATRIX: a kernel [K][N] row-major;

@@ -205,6 +205,10 @@ SIGNATURES = {
     "vtd_attention_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                        c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                        c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "vtd_layernorm_backward_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
+    "vtd_layernorm_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                       c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]),
     "vtd_adam_plan_bytes":(c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int,
                                     ctypes.POINTER(c_size_t), ctypes.POINTER(c_int)]),
     "vtd_adam_plan_upload": (c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int, c_void_p,

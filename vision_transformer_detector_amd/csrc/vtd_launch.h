@@ -79,6 +79,13 @@ int act_grad_launch(const float* z, int ldz, const float* ga, int ldga, int64_t 
 int head_unscatter_launch(const float* dU, int B, int T, int ldu, void* y, int ldy, int dtype,
                           hipStream_t st);
 
+// ----------------------------------------------------------------- vtd_layernorm_bwd.hip
+int layernorm_backward_workspace_bytes(int64_t rows, int D, size_t* bytes);
+int layernorm_backward_launch(const float* x, int ldx, const float* stat, const float* gamma,
+                              const float* dy, int lddy, const float* add, int ldadd,
+                              int64_t rows, int D, float* dx, int lddx, float* dgamma,
+                              float* dbeta, void* ws, size_t ws_bytes, hipStream_t st);
+
 // ----------------------------------------------------------------- vtd_mx8.hip
 int quantize_mx8_launch(const void* x, int x_dtype, int64_t rows, int K, int ldx, int Kq,
                         uint8_t* q, int ldq, uint8_t* s, int64_t s_rows, hipStream_t st);
