@@ -717,6 +717,65 @@ int vtd_layernorm_backward(const float* x_dev, int ldx, const float* stat_dev,
                            int lddx, float* dgamma_dev, float* dbeta_dev, void* ws_dev,
                            size_t ws_bytes, void* stream);
 
+/* ---- encoder block backward (additions to ABI 17; DESIGN.md "Encoder block backward")
+ * One encoder block of the reference with dropout=None (vtd.py:350-412):
+ *   x1 = x + MultiHeadAttention(LN1(x)),  y = x1 + MLP(LN2(x1)),
+ * LayerNormalization epsilon 1e-3, attention scale 1 / sqrt(key_dim), the MLP of
+ * mlp_quantities Dense + activation layers of widths d 2^(q-1) ... d.  dtype VTD_BF16X3 or
+ * VTD_BF16 (any other value: VTD_ERR_UNSUPPORTED): every Dense product and the attention core
+ * run in that mode's operands; the residual stream x, x1, y and its gradient are fp32 in both.
+ *
+ * vtd_block_params: the block's weights, const fp32 device arrays in the Keras layout, unpadded:
+ * ln1 / ln2 gamma, beta [d]; wq, wk, wv [d][num_heads][key_dim], bq, bk, bv [num_heads][key_dim];
+ * wo [num_heads][key_dim][d], bo [d]; w_mlp[j] [K_j][N_j] (K_0 = d, K_j = N_{j-1}), b_mlp[j]
+ * [N_j].  vtd_block_grads: outputs of the same shapes, and dx fp32 [rows][d] = d loss / d x
+ * (nullable: not written). */
+typedef struct vtd_block_dims {   /* one encoder block, vtd.py:350-412 */
+  int batch, tokens;              /* rows = batch * tokens */
+  int d, num_heads, key_dim;
+  int mlp_quantities;             /* widths d * 2^(q-1) ... d, as the reference */
+  int use_mish;                   /* 1 Mish, 0 tanh-GELU */
+  int dtype;                      /* VTD_BF16X3 | VTD_BF16 */
+} vtd_block_dims;
+typedef struct vtd_block_params {
+  const float* ln1_gamma; const float* ln1_beta;
+  const float* wq; const float* bq; const float* wk; const float* bk;
+  const float* wv; const float* bv; const float* wo; const float* bo;
+  const float* ln2_gamma; const float* ln2_beta;
+  const float* w_mlp[VTD_MAX_MLP]; const float* b_mlp[VTD_MAX_MLP];
+} vtd_block_params;
+typedef struct vtd_block_grads {
+  float* ln1_gamma; float* ln1_beta;
+  float* wq; float* bq; float* wk; float* bk;
+  float* wv; float* bv; float* wo; float* bo;
+  float* ln2_gamma; float* ln2_beta;
+  float* w_mlp[VTD_MAX_MLP]; float* b_mlp[VTD_MAX_MLP];
+  float* dx;
+} vtd_block_grads;
+/* One call: the training forward of the block from x_dev (fp32 [rows][d], unpadded) keeping
+ * every pre-activation in the workspace (the LayerNorm statistics, LN outputs in operand form,
+ * qkv, the attention output and its lse, x1, every MLP z_j and activation), then the backward
+ * from dy_dev (fp32 [rows][d] = d loss / d y) into *grads, in the order MLP (vtd_act_grad,
+ * vtd_gemm_wgrad, input-gradient vtd_gemm), LayerNorm 2 with the residual gradient as `add`,
+ * attention-output Dense, vtd_attention_backward, query/key/value Dense, LayerNorm 1 with the
+ * residual gradient.  y_dev (nullable): the block's output, fp32 [rows][d].  dy_dev NULL (y_dev
+ * then required, grads ignored): the training forward alone; the same launches, so y has the
+ * same bits either way.  Weights change every step, so the call converts what it needs into the
+ * workspace itself: the three query/key/value kernels are gathered into both operand forms of
+ * the fused, per-head padded matrix, wo likewise, and the fused gradients are un-gathered into
+ * the Keras-shaped outputs.  Asynchronous on `stream` (one stream), no allocation, no host
+ * synchronisation, no atomics, bit-identical from run to run.
+ * VTD_ERR_INVALID_ARG before any device call: a null dims / params / x / workspace / weight
+ * pointer (with dy_dev: grads and any gradient pointer but dx; without: y_dev), non-positive
+ * sizes, mlp_quantities > VTD_MAX_MLP, key_dim > 128, an MLP width of 2^24 or more,
+ * batch * tokens >= 2^31; VTD_ERR_UNSUPPORTED: a dtype other than the two;
+ * ws_bytes < vtd_encoder_block_backward_workspace_bytes: VTD_ERR_WORKSPACE. */
+int vtd_encoder_block_backward_workspace_bytes(const vtd_block_dims* dims, size_t* bytes);
+int vtd_encoder_block_backward(const vtd_block_dims* dims, const vtd_block_params* params,
+                               const float* x_dev, const float* dy_dev, float* y_dev,
+                               const vtd_block_grads* grads, void* ws, size_t ws_bytes,
+                               void* stream);
+
 /* ---- optimizer step: keras.optimizers.Adam + the ClipWeight constraint + the operand re-pack
  * One tensor of the table: w, m, v (updated in place) and g (read only), fp32 device arrays
  * in the Keras layout with 16-B aligned bases.  VTD_ADAM_MATRIX: a kernel [K][N] row-major;

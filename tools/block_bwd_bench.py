@@ -1,13 +1,27 @@
-"""Encoder-block backward micro-benchmark through the C-ABI.  The rows it measures now are the
-LayerNorm backward's: us per call of vtd_layernorm_backward at
+"""Encoder-block backward micro-benchmark through the C-ABI.
+
+LayerNorm rows (--what ln): us per call of vtd_layernorm_backward at
   C2    rows 256 * 196, D 768
   long  rows 32 * 1600, D 768
 with and without `add`, with and without dgamma / dbeta, next to the backward of
 torch.nn.functional.layer_norm on the same device and shapes.  The yardstick is bytes moved over
 time: x, dy (and add) read once and dx written once, 16 B per element with add and 12 B without.
+
+Block rows (--what block): one encoder block of 12 heads x 64, q = 3 at the same two shapes
+(C2: B 256, N 196; long: B 32, N 1600), in both operand modes: vtd_encoder_block_backward
+forward-only and forward + backward; in the same session every component call the chain is made
+of (vtd_layernorm_stats, vtd_layernorm, vtd_gemm, vtd_attention_train, vtd_act_forward,
+vtd_act_grad, vtd_gemm_wgrad, vtd_layernorm_backward, vtd_attention_backward, each timed on its
+own at the chain's shapes and summed: "parts_forward", "parts_forward_backward"), so that the
+chain's own work -- weight gathers and conversions, bias pads, memsets, the un-gathers, y = x1 +
+act(z) -- shows as the difference; and in bfloat16 a torch block with the same graph
+(layer_norm, linear, scaled_dot_product_attention, tanh-GELU) forward + backward as the vendor
+yardstick.
+
 Device events around every call, 3 warm-up calls, `--rounds` interleaved rounds of `--reps`
 calls each: the spread is over the rounds' means (the method of tools/attn_bwd_bench.py).
-  python tools/block_bwd_bench.py [--reps 10] [--rounds 3] [--shapes C2,long] [--out FILE.json]"""
+  python tools/block_bwd_bench.py [--what ln,block] [--reps 10] [--rounds 3] [--shapes C2,long]
+                                  [--out FILE.json]"""
 import argparse
 import ctypes
 import json
@@ -20,6 +34,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vision_transformer_detector_amd import _lib as L  # noqa: E402
 
 SHAPES = {"C2": (256 * 196, 768), "long": (32 * 1600, 768)}
+BLOCK_SHAPES = {"C2": (256, 196), "long": (32, 1600)}       # (B, N); d 768, 12 x 64, q 3
+D_MODEL, HEADS, KEY_DIM, MLP_Q = 768, 12, 64, 3
 EPS = 1e-3
 
 
@@ -79,8 +95,199 @@ def torch_calls(rows, D, dev):
             "torch:dx_only": (lambda: torch.autograd.grad(y, (x,), dy, retain_graph=True), 12)}
 
 
+def block_chain_calls(B, N, mode, dev):
+    """{name: call} of vtd_encoder_block_backward, forward-only and forward + backward."""
+    from vision_transformer_detector_amd import encoder
+    d, q = D_MODEL, MLP_Q
+    g = torch.Generator(device=dev).manual_seed(1)
+    w = []
+    for shape in encoder.weight_shapes(d, HEADS, KEY_DIM, q):
+        if len(shape) == 1 or shape == (HEADS, KEY_DIM):
+            t = 0.05 * torch.randn(shape, generator=g, device=dev)
+        else:
+            t = torch.randn(shape, generator=g, device=dev) / (shape[0] if len(shape) == 2 else d) ** 0.5
+        w.append(t)
+    w[0] += 1.0
+    w[10] += 1.0
+    x = torch.randn(B, N, d, generator=g, device=dev)
+    dy = torch.randn(B, N, d, generator=g, device=dev)
+    dims = encoder.block_dims(B, N, d, HEADS, KEY_DIM, q, False, mode)
+    ws = torch.empty(encoder.workspace_bytes(dims), device=dev, dtype=torch.uint8)
+    out = (torch.empty_like(x), [torch.empty_like(t) for t in w], torch.empty_like(x))
+    return {"vtd:forward": lambda: encoder.run(x, w, dims, ws=ws, out=out),
+            "vtd:forward_backward": lambda: encoder.run(x, w, dims, dy=dy, want_y=False, ws=ws,
+                                                        out=out)}, (w, x, dy, ws, out)
+
+
+def block_part_calls(B, N, mode, dev):
+    """([forward calls], [backward calls]): every library call the chain makes at its shapes, on
+    operands of the chain's formats (their values do not matter to the time)."""
+    x3 = mode == "bf16x3"
+    dt = L.BF16X3 if x3 else L.BF16
+    R, d, inner, qkv = B * N, D_MODEL, HEADS * KEY_DIM, 3 * HEADS * KEY_DIM
+    units = [d << (MLP_Q - 1 - j) for j in range(MLP_Q)]
+    ka = (lambda k: 2 * k) if x3 else (lambda k: k)
+    kk = (lambda k: 3 * k) if x3 else (lambda k: k)
+    umax = max(units + [qkv])
+    g = torch.Generator(device=dev).manual_seed(2)
+    f32 = [torch.randn(R, umax, generator=g, device=dev) for _ in range(3)]       # z, g, out
+    opA = (0.5 * torch.randn(R, ka(umax), generator=g, device=dev)).to(torch.bfloat16)
+    opG = (0.5 * torch.randn(R, ka(umax), generator=g, device=dev)).to(torch.bfloat16)
+    opO = (0.5 * torch.randn(R, ka(umax), generator=g, device=dev)).to(torch.bfloat16)
+    wt = (0.02 * torch.randn(umax * kk(max(units)), generator=g, device=dev)).to(torch.bfloat16)
+    bias = torch.zeros(umax, device=dev)
+    vec = 1 + 0.1 * torch.randn(d, generator=g, device=dev)
+    stat = torch.empty(R, 2, device=dev)
+    dW = torch.empty(max(units) * max(units), device=dev)
+    db = torch.empty(umax, device=dev)
+    lse = torch.empty(B * HEADS * N, device=dev)
+    st = L.stream_ptr()
+    n = L.c_size_t(0)
+    L.check(L.lib.vtd_layernorm_backward_workspace_bytes(R, d, ctypes.byref(n)))
+    ln_ws = torch.empty(n.value, device=dev, dtype=torch.uint8)
+    L.check(L.lib.vtd_attention_backward_workspace_bytes(B, N, HEADS, KEY_DIM, dt, ctypes.byref(n)))
+    at_ws = torch.empty(max(n.value, 16), device=dev, dtype=torch.uint8)
+    wg_shapes = [(units[j - 1] if j else d, units[j]) for j in range(MLP_Q)] + [(inner, d), (d, qkv)]
+    part = torch.empty(max(L.lib.vtd_gemm_wgrad_choice(R, K, Nn, dt) * (K + 1) * Nn
+                           for K, Nn in wg_shapes), device=dev)
+    scale = KEY_DIM ** -0.5
+    # the attention kernels read qkv [R][qkv] and dO [R][inner] as fp32 (bf16x3) or bf16
+    att_in = torch.randn(R, qkv, generator=g, device=dev).to(torch.float32 if x3 else torch.bfloat16)
+    att_do = torch.randn(R, inner, generator=g, device=dev).to(torch.float32 if x3 else torch.bfloat16)
+    att_code = L.F32 if x3 else L.BF16
+    L.check(L.lib.vtd_layernorm_stats(f32[0].data_ptr(), L.F32, R, d, umax, EPS, stat.data_ptr(), st))
+    keep = [f32, opA, opG, opO, wt, bias, vec, stat, dW, db, lse, ln_ws, at_ws, part, att_in, att_do]
+
+    def gemm(Nn, K, A, lda, out, ldo, out_dtype, with_bias, resid=None):
+        e = L.VtdEpilogue(bias=bias.data_ptr() if with_bias else None, act=L.ACT_NONE,
+                          resid=resid.data_ptr() if resid is not None else None, ldr=umax,
+                          out=out.data_ptr(), ldo=ldo, out_dtype=out_dtype)
+        keep.append(e)
+        return lambda: L.check(L.lib.vtd_gemm(R, Nn, K, A.data_ptr(), lda, wt.data_ptr(), K, dt,
+                                              ctypes.byref(e), st))
+
+    def wgrad(K, Nn, ldx, ldg):
+        ms = L.lib.vtd_gemm_wgrad_choice(R, K, Nn, dt)
+        return lambda: L.check(L.lib.vtd_gemm_wgrad(
+            R, K, Nn, opA.data_ptr(), ldx, opG.data_ptr(), ldg, dt, dW.data_ptr(), Nn,
+            db.data_ptr(), part.data_ptr(), part.numel() * 4, ms, st))
+
+    stats = lambda: L.check(L.lib.vtd_layernorm_stats(  # noqa: E731
+        f32[0].data_ptr(), L.F32, R, d, umax, EPS, stat.data_ptr(), st))
+    ln = lambda: L.check(L.lib.vtd_layernorm(  # noqa: E731
+        f32[0].data_ptr(), L.F32, R, d, umax, vec.data_ptr(), vec.data_ptr(), EPS,
+        opA.data_ptr(), ka(d), dt, st))
+    fwd = [stats, ln, stats, ln,
+           gemm(qkv, kk(d), opA, ka(d), att_in, qkv, att_code, True),
+           lambda: L.check(L.lib.vtd_attention_train(
+               att_in.data_ptr(), B, N, HEADS, KEY_DIM, qkv, scale,
+               opO.data_ptr(), ka(inner), lse.data_ptr(), dt, st)),
+           gemm(d, kk(inner), opO, ka(inner), f32[2], umax, L.F32, True, resid=f32[1])]
+    k = d
+    for j, u in enumerate(units):
+        fwd.append(gemm(u, kk(k), opA, ka(k), f32[2], umax, L.F32, True))
+        if j + 1 < MLP_Q:
+            fwd.append(lambda u=u: L.check(L.lib.vtd_act_forward(
+                f32[0].data_ptr(), R, u, umax, L.ACT_GELU_TANH, opA.data_ptr(), ka(u), dt, st)))
+        k = u
+    bwd = []
+    for j in range(MLP_Q - 1, -1, -1):
+        u, kin = units[j], (units[j - 1] if j else d)
+        bwd.append(lambda u=u: L.check(L.lib.vtd_act_grad(
+            f32[0].data_ptr(), umax, f32[1].data_ptr(), umax, R, u, L.ACT_GELU_TANH,
+            opG.data_ptr(), ka(u), dt, st)))
+        bwd.append(wgrad(kin, u, ka(kin), ka(u)))
+        bwd.append(gemm(kin, kk(u), opG, ka(u), f32[2], umax, L.F32, False))
+    lnb = lambda: L.check(L.lib.vtd_layernorm_backward(  # noqa: E731
+        f32[0].data_ptr(), umax, stat.data_ptr(), vec.data_ptr(), f32[1].data_ptr(), umax,
+        f32[2].data_ptr(), umax, R, d, f32[2].data_ptr(), umax, db.data_ptr(), db.data_ptr() + 4 * d,
+        ln_ws.data_ptr(), ln_ws.numel(), st))
+    bwd += [lnb,
+            lambda: L.check(L.lib.vtd_act_forward(f32[0].data_ptr(), R, d, umax, L.ACT_NONE,
+                                                  opG.data_ptr(), ka(d), dt, st)),
+            wgrad(inner, d, ka(inner), ka(d)),
+            gemm(inner, kk(d), opG, ka(d), att_do, inner, att_code, False),
+            lambda: L.check(L.lib.vtd_attention_backward(
+                att_in.data_ptr(), opO.data_ptr(), att_do.data_ptr(), lse.data_ptr(), B, N, HEADS,
+                KEY_DIM, qkv, ka(inner), inner, scale,
+                opG.data_ptr(), ka(qkv), dt, at_ws.data_ptr(), at_ws.numel(), st)),
+            wgrad(d, qkv, ka(d), ka(qkv)),
+            gemm(d, kk(qkv), opG, ka(qkv), f32[2], umax, L.F32, False),
+            lnb]
+    return fwd, bwd, keep
+
+
+def torch_block_call(B, N, dev):
+    """A bf16 torch block with the chain's graph, forward + backward (all gradients)."""
+    F = torch.nn.functional
+    d, inner = D_MODEL, HEADS * KEY_DIM
+    g = torch.Generator(device=dev).manual_seed(3)
+    mk = lambda *s: (torch.randn(*s, generator=g, device=dev) / s[-1] ** 0.5).to(  # noqa: E731
+        torch.bfloat16).requires_grad_(True)
+    vec = lambda n: torch.ones(n, device=dev, dtype=torch.bfloat16).requires_grad_(True)  # noqa: E731
+    g1, b1, g2, b2 = vec(d), vec(d), vec(d), vec(d)
+    wqkv, bqkv, wo, bo = mk(3 * inner, d), vec(3 * inner), mk(d, inner), vec(d)
+    units = [d << (MLP_Q - 1 - j) for j in range(MLP_Q)]
+    mlp, k = [], d
+    for u in units:
+        mlp.append((mk(u, k), vec(u)))
+        k = u
+    x = torch.randn(B, N, d, generator=g, device=dev).to(torch.bfloat16).requires_grad_(True)
+    dy = torch.randn(B, N, d, generator=g, device=dev).to(torch.bfloat16)
+    leaves = [x, g1, b1, g2, b2, wqkv, bqkv, wo, bo] + [t for p in mlp for t in p]
+
+    def call():
+        h = F.layer_norm(x, (d,), g1, b1, eps=EPS)
+        qkv = F.linear(h, wqkv, bqkv).view(B, N, 3, HEADS, KEY_DIM).permute(2, 0, 3, 1, 4)
+        o = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2])
+        x1 = x + F.linear(o.transpose(1, 2).reshape(B, N, inner), wo, bo)
+        a = F.layer_norm(x1, (d,), g2, b2, eps=EPS)
+        for wj, bj in mlp:
+            a = F.gelu(F.linear(a, wj, bj), approximate="tanh")
+        torch.autograd.grad(x1 + a, leaves, dy)
+    return call
+
+
+def block_rows(name, a, dev):
+    """The block records of one shape: both modes, chain / sum of parts / torch."""
+    B, N = BLOCK_SHAPES[name]
+    results = []
+    for mode in ("bfloat16", "bf16x3"):
+        chain, keep = block_chain_calls(B, N, mode, dev)
+        fwd, bwd, keep2 = block_part_calls(B, N, mode, dev)
+        calls = dict(chain)
+        if mode == "bfloat16":
+            calls["torch:forward_backward"] = torch_block_call(B, N, dev)
+        for f in list(calls.values()) + fwd + bwd:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        us = {n: [] for n in list(calls) + ["vtd:parts_forward", "vtd:parts_forward_backward"]}
+        for _ in range(a.rounds):
+            for n, f in calls.items():
+                us[n].append(timed(f, a.reps))
+            tf = sum(timed(f, a.reps) for f in fwd)
+            us["vtd:parts_forward"].append(tf)
+            us["vtd:parts_forward_backward"].append(tf + sum(timed(f, a.reps) for f in bwd))
+        for n, v in us.items():
+            who, what = n.split(":")
+            rec = {"kernel": "encoder_block", "shape": name, "rows": B * N, "D": D_MODEL,
+                   "heads": HEADS, "key_dim": KEY_DIM, "mlp_quantities": MLP_Q, "mode": mode,
+                   "impl": who, "call": what, "us_mean": round(sum(v) / len(v), 1),
+                   "us_min": round(min(v), 1), "us_max": round(max(v), 1), "rounds": a.rounds,
+                   "reps": a.reps}
+            if what.startswith("parts"):
+                rec["launches"] = len(fwd) + (len(bwd) if what.endswith("backward") else 0)
+            results.append(rec)
+            print(json.dumps(rec), flush=True)
+        del chain, keep, fwd, bwd, keep2, calls
+        torch.cuda.empty_cache()
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--what", default="ln,block", help="ln, block or both")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--shapes", default="C2,long")
@@ -88,7 +295,9 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     results = []
-    for name in a.shapes.split(","):
+    for name in a.shapes.split(",") if "block" in a.what.split(",") else []:
+        results += block_rows(name, a, dev)
+    for name in a.shapes.split(",") if "ln" in a.what.split(",") else []:
         rows, D = SHAPES[name]
         calls, keep = library_calls(rows, D, dev)
         calls.update(torch_calls(rows, D, dev))

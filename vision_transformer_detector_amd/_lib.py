@@ -100,6 +100,23 @@ class VtdHeadGrads(ctypes.Structure):
     _fields_ = VtdHeadParams._fields_ + [("d_encoded", c_void_p)]
 
 
+class VtdBlockDims(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("batch", "tokens", "d", "num_heads", "key_dim",
+                                     "mlp_quantities", "use_mish", "dtype")]
+
+
+class VtdBlockParams(ctypes.Structure):
+    """vtd_block_params (one encoder block's fp32 Keras-layout weights) and, with the extra dx
+    field, vtd_block_grads (VtdBlockGrads below)."""
+    _fields_ = ([(n, c_void_p) for n in ("ln1_gamma", "ln1_beta", "wq", "bq", "wk", "bk", "wv",
+                                         "bv", "wo", "bo", "ln2_gamma", "ln2_beta")] +
+                [("w_mlp", c_void_p * MAX_MLP), ("b_mlp", c_void_p * MAX_MLP)])
+
+
+class VtdBlockGrads(ctypes.Structure):
+    _fields_ = VtdBlockParams._fields_ + [("dx", c_void_p)]
+
+
 ADAM_MATRIX, ADAM_VECTOR = 0, 1
 
 
@@ -209,6 +226,12 @@ SIGNATURES = {
     "vtd_layernorm_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                        c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vtd_encoder_block_backward_workspace_bytes": (c_int, [ctypes.POINTER(VtdBlockDims),
+                                                           ctypes.POINTER(c_size_t)]),
+    "vtd_encoder_block_backward": (c_int, [ctypes.POINTER(VtdBlockDims),
+                                           ctypes.POINTER(VtdBlockParams), c_void_p, c_void_p,
+                                           c_void_p, ctypes.POINTER(VtdBlockGrads), c_void_p,
+                                           c_size_t, c_void_p]),
     "vtd_adam_plan_bytes":(c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int,
                                     ctypes.POINTER(c_size_t), ctypes.POINTER(c_int)]),
     "vtd_adam_plan_upload": (c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int, c_void_p,

@@ -86,6 +86,32 @@ int layernorm_backward_launch(const float* x, int ldx, const float* stat, const 
                               int64_t rows, int D, float* dx, int lddx, float* dgamma,
                               float* dbeta, void* ws, size_t ws_bytes, hipStream_t st);
 
+// ----------------------------------------------------------------- vtd_block_bwd.hip
+// A padded matrix Wp [Kp][Np] made of up to three Keras tensors src[part] [K][N] side by side
+// along n (part width part_np), with group padding on either axis: source row (k / kgp) kg +
+// k % kgp for k % kgp < kg, source column likewise from n % part_np with ng / ngp; every other
+// element is zero.  query/key/value: K = kg = d, kgp = Kp = d_p, N = heads key_dim, ng =
+// key_dim, ngp = dkp, part_np = inner_p, 3 parts; attention_output: K = heads key_dim, kg =
+// key_dim, kgp = dkp, N = ng = d, ngp = part_np = Np = d_p, 1 part.
+struct BlockGather {
+  const float* src[3];
+  int nparts, K, N, kg, kgp, ng, ngp, part_np, Kp, Np;
+};
+// Wp in the operand dtype (bf16, or the split B operand [hi | hi | lo], the conversions of
+// split_bf16x3 role 1): dst_t = Wp^T [Np][kk(Kp)] (a forward GEMM's Bt), dst_kn = Wp
+// [Kp][kk(Np)] (an input-gradient GEMM's Bt); either may be null.  Every pad is written as zero.
+int block_gather_launch(const BlockGather& g, void* dst_t, void* dst_kn, int dtype,
+                        hipStream_t st);
+// the biases (K = kg = kgp = 1) -> the padded fp32 vector [Np]
+int block_gather_bias_launch(const BlockGather& g, float* dst, hipStream_t st);
+// the inverse on fp32 gradients: W [Kp][ldw] (and b [Np], nullable) -> dst[part] [K][N]
+// (dstb[part] [N]); g.src is not read
+int block_ungather_launch(const BlockGather& g, float* const* dst, float* const* dstb,
+                          const float* W, int ldw, const float* b, hipStream_t st);
+// y = x1 + act(z), fp32 [rows][D]
+int block_resid_act_launch(const float* x1, int ldx, const float* z, int ldz, int64_t rows, int D,
+                           int act, float* y, int ldy, hipStream_t st);
+
 // ----------------------------------------------------------------- vtd_mx8.hip
 int quantize_mx8_launch(const void* x, int x_dtype, int64_t rows, int K, int ldx, int Kq,
                         uint8_t* q, int ldq, uint8_t* s, int64_t s_rows, hipStream_t st);

@@ -604,6 +604,21 @@ class Model:
             names += [f"dense_{j + 1}/kernel", f"dense_{j + 1}/bias"]
         return names + ["MLP_Head_no_Sigmoid/kernel", "MLP_Head_no_Sigmoid/bias"]
 
+    def encoder_block_weights(self, i: int):
+        """The weights of encoder block i (0 <= i < encoder_repeat_times) as `encoder_block`
+        takes them: an OrderedDict of Keras name -> fp32 device tensor in the Keras shape, in
+        creation order (ln1 gamma, beta; query, key, value, attention_output kernel and bias;
+        ln2 gamma, beta; the MLP kernel / bias pairs).  Fresh copies of the model's current
+        weights -- ordinary tensors, the caller sets requires_grad; the packed buffers of the
+        forward are not touched."""
+        reps = self.kwargs["encoder_repeat_times"]
+        if not isinstance(i, int) or not 0 <= i < reps:
+            raise ValueError(f"encoder_block_weights: block index {i!r} must be an int in "
+                             f"[0, {reps})")
+        per = 12 + 2 * self.kwargs["encoder_mlp_quantities"]
+        names = list(self.weight_shapes)[3 + i * per: 3 + (i + 1) * per]
+        return OrderedDict((n, self._master[n].to(self.device).contiguous()) for n in names)
+
     def _head_master(self):
         """fp32 device copies of the head's weights in the Keras layout (vtd_head_params),
         made once per set_weights."""
