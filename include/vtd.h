@@ -776,6 +776,42 @@ int vtd_encoder_block_backward(const vtd_block_dims* dims, const vtd_block_param
                                const vtd_block_grads* grads, void* ws, size_t ws_bytes,
                                void* stream);
 
+/* ---- patch embedding backward (additions to ABI 17; DESIGN.md "Whole-model gradients")
+ * The stem of the reference (transformer_preprocessor, vtd.py:271-307):
+ *   x0[b N + n][j] = sum_k patches[b N + n][k] W[k][j] + bias[j] + pos[n],
+ * patches by tf.image.extract_patches (SAME zero pad, (kh, kw, c) order), the position
+ * embedding Keras's (tokens, 1), broadcast over d.  tokens = ceil(H / patch) ceil(W / patch) and
+ * patch_dim = patch^2 C are derived inside.  dtype VTD_BF16X3 or VTD_BF16 (any other value:
+ * VTD_ERR_UNSUPPORTED): the operands of the two products; x0 and every gradient are fp32.
+ * vtd_stem_params: const fp32 device arrays in the Keras layout, unpadded: pos [tokens], w
+ * [patch_dim][d], b [d].  vtd_stem_grads: outputs of the same shapes. */
+typedef struct vtd_stem_dims {
+  int batch, H, W, C;             /* images fp32 [batch][H][W][C] */
+  int patch, d;
+  int dtype;                      /* VTD_BF16X3 | VTD_BF16 */
+} vtd_stem_dims;
+typedef struct vtd_stem_params { const float* pos; const float* w; const float* b; } vtd_stem_params;
+typedef struct vtd_stem_grads { float* pos; float* w; float* b; } vtd_stem_grads;
+/* Forward only (dx0_dev NULL; x0_dev required, grads ignored): vtd_extract_patches into the
+ * workspace in the mode's operand form, the kernel converted to W^T there (weights change every
+ * step), one vtd_gemm with the bias and the rowadd epilogue into x0_dev, fp32 [batch tokens][d],
+ * unpadded.  Backward (dx0_dev fp32 [batch tokens][d] = d loss / d x0): the patches again; when
+ * x0_dev is given also the rest of the forward, the same launches, so x0 has the same bits
+ * either way; then one pass over dx0 that writes its rows in operand form (exactly what
+ * vtd_act_forward(VTD_ACT_NONE) writes) and their sums, vtd_gemm_wgrad for grads->w and
+ * grads->b, and grads->pos[n] = the row sums added over the batch in order.  Asynchronous on
+ * `stream` (one stream), no allocation, no host synchronisation, no atomics, bit-identical from
+ * run to run; exactly the elements of the outputs are written.
+ * VTD_ERR_INVALID_ARG before any device call: a null dims / params / images / workspace / weight
+ * pointer (with dx0_dev: grads and any gradient pointer; without: x0_dev), non-positive sizes,
+ * batch * tokens >= 2^31, d or patch_dim of 2^24 or more, a workspace, x0, params->w or
+ * params->b not 16-byte aligned or any other array not 4-byte aligned; VTD_ERR_UNSUPPORTED: a
+ * dtype other than the two; ws_bytes < vtd_stem_backward_workspace_bytes: VTD_ERR_WORKSPACE. */
+int vtd_stem_backward_workspace_bytes(const vtd_stem_dims* dims, size_t* bytes);
+int vtd_stem_backward(const vtd_stem_dims* dims, const vtd_stem_params* params,
+                      const float* images_dev, const float* dx0_dev, float* x0_dev,
+                      const vtd_stem_grads* grads, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- optimizer step: keras.optimizers.Adam + the ClipWeight constraint + the operand re-pack
  * One tensor of the table: w, m, v (updated in place) and g (read only), fp32 device arrays
  * in the Keras layout with 16-B aligned bases.  VTD_ADAM_MATRIX: a kernel [K][N] row-major;

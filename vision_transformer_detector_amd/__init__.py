@@ -42,6 +42,7 @@ from .loss import (ciou_calculator, diagonal_calculator, get_label_arrays,  # no
 from .attention import attention_core  # noqa: F401
 from .layernorm import layer_norm  # noqa: F401
 from .encoder import encoder_block  # noqa: F401
+from .stem import patch_embedding  # noqa: F401
 from . import optimizers, presets  # noqa: F401
 from .optimizers import _allowed_decay_times, learning_rate_step_decay  # noqa: F401
 from .preprocess import get_image_tensors  # noqa: F401
@@ -52,4 +53,4 @@ __all__ = ["Constants", "Model", "create_vision_transformer_detector",
            "my_custom_loss", "loss_components", "loss_and_grad", "ciou_calculator",
            "diagonal_calculator", "get_label_arrays", "optimizers",
            "learning_rate_step_decay", "attention_core", "layer_norm", "encoder_block",
-           "enable_device_kernel_arguments"]
+           "patch_embedding", "enable_device_kernel_arguments"]

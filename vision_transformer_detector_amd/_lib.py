@@ -117,6 +117,15 @@ class VtdBlockGrads(ctypes.Structure):
     _fields_ = VtdBlockParams._fields_ + [("dx", c_void_p)]
 
 
+class VtdStemDims(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("batch", "H", "W", "C", "patch", "d", "dtype")]
+
+
+class VtdStemParams(ctypes.Structure):
+    """vtd_stem_params (the patch embedding's fp32 Keras-layout weights) and vtd_stem_grads."""
+    _fields_ = [(n, c_void_p) for n in ("pos", "w", "b")]
+
+
 ADAM_MATRIX, ADAM_VECTOR = 0, 1
 
 
@@ -232,6 +241,11 @@ SIGNATURES = {
                                            ctypes.POINTER(VtdBlockParams), c_void_p, c_void_p,
                                            c_void_p, ctypes.POINTER(VtdBlockGrads), c_void_p,
                                            c_size_t, c_void_p]),
+    "vtd_stem_backward_workspace_bytes": (c_int, [ctypes.POINTER(VtdStemDims),
+                                                  ctypes.POINTER(c_size_t)]),
+    "vtd_stem_backward": (c_int, [ctypes.POINTER(VtdStemDims), ctypes.POINTER(VtdStemParams),
+                                  c_void_p, c_void_p, c_void_p, ctypes.POINTER(VtdStemParams),
+                                  c_void_p, c_size_t, c_void_p]),
     "vtd_adam_plan_bytes":(c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int,
                                     ctypes.POINTER(c_size_t), ctypes.POINTER(c_int)]),
     "vtd_adam_plan_upload": (c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int, c_void_p,

@@ -640,6 +640,85 @@ class Model:
         dtype 'bf16x3' or 'bfloat16'."""
         return self._head_pass("head_gradients", images, y_true, encoded)
 
+    # ---- whole-model gradients (vtd_stem_backward, vtd_encoder_block_backward, vtd_head_backward)
+    def stem_weights(self):
+        """The weights of the patch embedding as `patch_embedding` takes them: an OrderedDict of
+        Keras name -> fp32 device tensor in the Keras shape, in creation order (the position
+        embedding (tokens, 1), the linear_projection kernel and bias).  Fresh copies of the
+        model's current weights, as `encoder_block_weights` returns a block's."""
+        names = list(self.weight_shapes)[:3]
+        return OrderedDict((n, self._master[n].to(self.device).contiguous()) for n in names)
+
+    def _encoder_master(self):
+        """fp32 device copies of the stem's and every encoder block's weights in the Keras
+        layout (vtd_stem_params, vtd_block_params), made once per set_weights."""
+        if getattr(self, "_enc_dev_of", None) is not self._master:
+            per = 12 + 2 * self.kwargs["encoder_mlp_quantities"]
+            names = list(self.weight_shapes)[:3 + self.kwargs["encoder_repeat_times"] * per]
+            self._enc_dev = OrderedDict(
+                (n, self._master[n].to(self.device).contiguous()) for n in names)
+            self._enc_dev_of = self._master
+        return self._enc_dev
+
+    def gradients(self, images, y_true):
+        """The gradient of the compiled loss with respect to every weight: the training forward
+        of the whole model, the loss gradient at its logits, and the backward through the head,
+        every encoder block in reverse and the patch embedding.  Returns (out5, grads): out5 as
+        head_gradients returns it and `grads` an OrderedDict with exactly the keys of
+        `weight_names()`, in that order, of fp32 device tensors in the Keras shapes (the position
+        embedding (tokens, 1)).  The loss reported is that of the training-forward chain -- an
+        fp32 residual stream, every LayerNorm applied as written -- not of `model(images)`,
+        whose forward folds the LayerNorms into the next kernels and, in 'bfloat16', keeps a
+        bf16 residual stream; the two agree within the mode's forward tolerance.  Steps, all on
+        the current stream with no host read: vtd_stem_backward (forward only),
+        vtd_encoder_block_backward per block (forward only, every block input kept),
+        head_gradients' pass on the last block's output, then the blocks' backward calls in
+        reverse through one shared workspace and the stem's.  Needs compile(loss=my_custom_loss
+        or a functools.partial of it) and dtype 'bf16x3' or 'bfloat16'."""
+        if self.dtype not in (L.BF16X3, L.BF16):
+            raise ValueError("gradients: the head backward runs in the 'bf16x3' and "
+                             "'bfloat16' modes only (not float32 / float8)")
+        from . import loss as _loss
+        if self.loss is None or _loss.fused_loss_params(self.loss) is None:
+            raise ValueError("gradients: compile(loss=my_custom_loss or a functools.partial "
+                             "of it with keyword arguments) first")
+        from . import encoder as _enc
+        from . import stem as _stem
+        x = self._as_images(images)
+        b = x.shape[0]
+        kw, dims = self.kwargs, self.dims
+        reps, per = kw["encoder_repeat_times"], 12 + 2 * kw["encoder_mlp_quantities"]
+        sdims = L.VtdStemDims(batch=b, H=self.input_shape[0], W=self.input_shape[1],
+                              C=self.input_shape[2], patch=kw["patch_size"], d=dims.d,
+                              dtype=self.dtype)
+        bdims = L.VtdBlockDims(batch=b, tokens=dims.tokens, d=dims.d,
+                               num_heads=kw["encoder_num_heads"], key_dim=kw["encoder_key_dim"],
+                               mlp_quantities=kw["encoder_mlp_quantities"],
+                               use_mish=1 if kw["use_mish"] else 0, dtype=self.dtype)
+        with torch.cuda.device(self.device):
+            need = (_stem.workspace_bytes(sdims), _enc.workspace_bytes(bdims))
+            held = getattr(self, "_grad_ws", (None, None))
+            self._grad_ws = tuple(
+                t if t is not None and t.numel() >= n
+                else torch.empty(n, dtype=torch.uint8, device=self.device)
+                for t, n in zip(held, need))
+            stem_ws, block_ws = self._grad_ws
+            wdev = list(self._encoder_master().values())
+            sw = wdev[:3]
+            bw = [wdev[3 + i * per: 3 + (i + 1) * per] for i in range(reps)]
+            xs = [_stem.run(x, sw, sdims, ws=stem_ws)[0]]
+            for i in range(reps):
+                xs.append(_enc.run(xs[i], bw[i], bdims, ws=block_ws)[0])
+            out5, head = self._head_pass("gradients", None, y_true, xs[reps])
+            dy = head.pop("encoded_images")
+            found = []
+            for i in range(reps - 1, -1, -1):
+                _, g, dy = _enc.run(xs[i], bw[i], bdims, dy=dy, want_y=False, ws=block_ws)
+                found = g + found
+            _, g = _stem.run(x, sw, sdims, dx0=dy, want_x0=False, ws=stem_ws)
+            found = g + found + list(head.values())
+        return out5, OrderedDict(zip(self.weight_shapes, found))
+
     # ---- head training (vtd_adam_step; optimizers.py)
     def train_head_on_batch(self, images, y_true, encoded=None):
         """keras.Model.train_on_batch for the detection head on a frozen encoder: head_gradients'
