@@ -858,6 +858,75 @@ int vtd_adam_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
                   double learning_rate, float beta1, float beta2, float epsilon, float clipvalue,
                   int constrain, float max_weight, void* stream);
 
+/* ---- whole-model training step: the table entry that can express every operand Model._pack
+ * builds with vtd_pack_dense / vtd_pack_vector, a per-tensor destination format, constraint flag
+ * and update rule.  w, m, v, g as in vtd_adam_tensor.
+ *   VTD_ADAM_MATRIX [K][N]: element (k, n) goes to packed row
+ *     row_offset + (n / n_group) * n_group_p + n % n_group, packed column
+ *     k' = (k / k_group) * k_group_p + k % k_group (vtd_pack_dense's map; K % k_group == 0,
+ *     N % n_group == 0; k_group = K, n_group = N: no grouping).  The piece width K_p of a packed
+ *     row is ld (VTD_TRAIN_PACK_F32; VTD_TRAIN_PACK_MODE in VTD_BF16) or ld / 3
+ *     (VTD_TRAIN_PACK_MODE in VTD_BF16X3, rows [hi | hi | lo]); K_p % 8 == 0, K_p >= the last
+ *     real k' + 1, a 16-B aligned base.
+ *   VTD_ADAM_VECTOR [N]: element n goes to fp32 element row_offset + (n / n_group) * n_group_p
+ *     + n % n_group of `packed` (vtd_pack_vector's map; any non-NONE packed_dtype means fp32).
+ *   packed_dtype: VTD_TRAIN_PACK_NONE (packed must be null), VTD_TRAIN_PACK_MODE (the plan's
+ *     dtype: bf16 or split-bf16) or VTD_TRAIN_PACK_F32 (fp32 [N_p][K_p], the staging form
+ *     vtd_fold_layernorm reads).
+ *   constrain: 0 exempts the tensor from ClipWeight whatever the step asks for (the reference
+ *     leaves the position embedding unconstrained).
+ *   rule: VTD_TRAIN_RULE_DENSE is vtd_adam_step's; VTD_TRAIN_RULE_SPARSE is the order of Keras's
+ *     sparse Adam path, which an Embedding's gradient takes (every index once: a dense update):
+ *       m = m * beta1 + g * (1 - beta1);   v = v * beta2 + (g * g) * (1 - beta2)
+ *       w = w - (alpha * m) / (sqrt(v) + epsilon)            same alpha, g clipped first
+ * Padding rule: for every real n the step writes the whole piece(s) [0, K_p) of its packed row,
+ * zeros at every k' that is no image of a real k; packed rows that are no image of a real n
+ * (the pad rows inside a group, the rows of other tensors sharing the buffer) and everything
+ * outside the buffers stay untouched. */
+enum { VTD_TRAIN_PACK_NONE = 0, VTD_TRAIN_PACK_MODE = 1, VTD_TRAIN_PACK_F32 = 2 };
+enum { VTD_TRAIN_RULE_DENSE = 0, VTD_TRAIN_RULE_SPARSE = 1 };
+typedef struct vtd_train_tensor {
+  float* w; float* m; float* v; const float* g;
+  void* packed;
+  int kind, K, N, ld;
+  int k_group, k_group_p, n_group, n_group_p, row_offset;
+  int packed_dtype, constrain, rule;
+} vtd_train_tensor;
+/* The plan entries and the step: as vtd_adam_plan_bytes / vtd_adam_plan_upload / vtd_adam_step,
+ * over vtd_train_tensor (one launch for the whole table, every element owned by one thread, no
+ * atomics, no allocation, no host read in the step).  VTD_ERR_INVALID_ARG before any device call:
+ * everything the vtd_adam_* entries reject, and a bad packed_dtype / rule, packed_dtype NONE
+ * with a destination or a destination without one, VTD_TRAIN_PACK_MODE with a dtype other than
+ * VTD_BF16 / VTD_BF16X3, non-positive groups, k_group_p < k_group, n_group_p < n_group,
+ * K % k_group != 0, N % n_group != 0, a negative row_offset, ld too small for the last real k',
+ * K_p % 8 != 0. */
+int vtd_train_plan_bytes(const vtd_train_tensor* tensors, int n_tensors, int dtype, size_t* bytes,
+                         int* tiles);
+int vtd_train_plan_upload(const vtd_train_tensor* tensors, int n_tensors, int dtype,
+                          void* plan_dev, size_t plan_bytes, void* stream);
+int vtd_train_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
+                   double learning_rate, float beta1, float beta2, float epsilon, float clipvalue,
+                   int constrain, float max_weight, void* stream);
+
+/* The LayerNorm fold of several layers in ONE launch: job j is vtd_fold_layernorm(w32, N, K,
+ * ldw, gamma, beta, bias_in, w_out, ldo, dtype, bias_out, colsum) with the same per-row
+ * arithmetic, so the same bits.  vtd_fold_plan_upload checks the host table and copies it to
+ * plan_dev (caller-owned, 16-B aligned, plan_bytes >= n_jobs * sizeof(vtd_fold_job)), waits for
+ * the copy and returns the largest N in *max_rows; vtd_fold_layernorm_batch launches
+ * (max_rows / 4 rounded up) x n_jobs workgroups on `stream` with no copy, allocation or host
+ * synchronisation.  VTD_ERR_INVALID_ARG before any device call: null pointers (bias_in may be
+ * null), non-positive sizes, ldw < K, ldo < K, a dtype other than VTD_F32 / VTD_BF16, a
+ * misaligned or too small plan. */
+typedef struct vtd_fold_job {
+  const float* w32; const float* gamma; const float* beta; const float* bias_in;
+  void* w_out; float* bias_out; float* colsum;
+  int N, K, ldw, ldo;
+} vtd_fold_job;
+int vtd_fold_plan_upload(const vtd_fold_job* jobs, int n_jobs, int dtype, void* plan_dev,
+                         size_t plan_bytes, int* max_rows, void* stream);
+int vtd_fold_layernorm_batch(const void* plan_dev, int n_jobs, int max_rows, int dtype,
+                             void* stream);
+
 /* Optional per-kernel timing of vtd_forward (hipEvents on `stream`, recorded around
  * every launch while enabled).  vtd_profile_read returns per-class totals in ms
  * summed over the forwards since the last reset; classes: 0 gemm, 1 attention,

@@ -134,6 +134,22 @@ class VtdAdamTensor(ctypes.Structure):
                 ("packed", c_void_p), ("kind", c_int), ("K", c_int), ("N", c_int), ("ld", c_int)]
 
 
+TRAIN_PACK_NONE, TRAIN_PACK_MODE, TRAIN_PACK_F32 = 0, 1, 2
+TRAIN_RULE_DENSE, TRAIN_RULE_SPARSE = 0, 1
+
+
+class VtdTrainTensor(ctypes.Structure):
+    _fields_ = (VtdAdamTensor._fields_ +
+                [(n, c_int) for n in ("k_group", "k_group_p", "n_group", "n_group_p",
+                                      "row_offset", "packed_dtype", "constrain", "rule")])
+
+
+class VtdFoldJob(ctypes.Structure):
+    _fields_ = ([(n, c_void_p) for n in ("w32", "gamma", "beta", "bias_in", "w_out", "bias_out",
+                                         "colsum")] +
+                [(n, c_int) for n in ("N", "K", "ldw", "ldo")])
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "vtd_abi_version": (c_int, []),
@@ -252,6 +268,15 @@ SIGNATURES = {
                                      c_size_t, c_void_p]),
     "vtd_adam_step": (c_int, [c_void_p, c_int, c_int, c_int64, ctypes.c_double, c_float, c_float,
                               c_float, c_float, c_int, c_float, c_void_p]),
+    "vtd_train_plan_bytes": (c_int, [ctypes.POINTER(VtdTrainTensor), c_int, c_int,
+                                     ctypes.POINTER(c_size_t), ctypes.POINTER(c_int)]),
+    "vtd_train_plan_upload": (c_int, [ctypes.POINTER(VtdTrainTensor), c_int, c_int, c_void_p,
+                                      c_size_t, c_void_p]),
+    "vtd_train_step": (c_int, [c_void_p, c_int, c_int, c_int64, ctypes.c_double, c_float, c_float,
+                               c_float, c_float, c_int, c_float, c_void_p]),
+    "vtd_fold_plan_upload": (c_int, [ctypes.POINTER(VtdFoldJob), c_int, c_int, c_void_p, c_size_t,
+                                     ctypes.POINTER(c_int), c_void_p]),
+    "vtd_fold_layernorm_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "vtd_forward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdWeights), c_void_p,
                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vtd_set_knob": (c_int, [c_int, c_int]),

@@ -573,17 +573,16 @@ __global__ __launch_bounds__(1024) void ln_stats_finalize_s_kernel(const float2*
 
 // LayerNorm fold of one consumer Dense layer (one-time weight preparation): one wave per
 // output row n; fp64 sums (bias' from the fp32 W, colsum from the rounded stored W').
+// fold_ln_row: output row n by one wave -- the arithmetic both kernels below share, so that the
+// batched refresh after an optimizer step gives the bits of the one-time fold.
 template <typename TO>
-__global__ __launch_bounds__(256) void fold_ln_kernel(const float* __restrict__ w, int N, int K,
-                                                      int ldw, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta,
-                                                      const float* __restrict__ bias_in,
-                                                      TO* __restrict__ wo, int ldo,
-                                                      float* __restrict__ bias_out,
-                                                      float* __restrict__ colsum) {
-  const int lane = threadIdx.x & 63;
-  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (n >= N) return;
+__device__ __forceinline__ void fold_ln_row(const float* __restrict__ w, int n, int K, int ldw,
+                                            const float* __restrict__ gamma,
+                                            const float* __restrict__ beta,
+                                            const float* __restrict__ bias_in,
+                                            TO* __restrict__ wo, int ldo,
+                                            float* __restrict__ bias_out,
+                                            float* __restrict__ colsum, int lane) {
   double sb = 0.0, sc = 0.0;
   for (int k = lane; k < ldo; k += 64) {
     const float wk = k < K ? w[(int64_t)n * ldw + k] : 0.f;
@@ -602,6 +601,31 @@ __global__ __launch_bounds__(256) void fold_ln_kernel(const float* __restrict__ 
     bias_out[n] = (float)((double)(bias_in ? bias_in[n] : 0.f) + sb);
     colsum[n] = (float)sc;
   }
+}
+
+template <typename TO>
+__global__ __launch_bounds__(256) void fold_ln_kernel(const float* __restrict__ w, int N, int K,
+                                                      int ldw, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta,
+                                                      const float* __restrict__ bias_in,
+                                                      TO* __restrict__ wo, int ldo,
+                                                      float* __restrict__ bias_out,
+                                                      float* __restrict__ colsum) {
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  fold_ln_row<TO>(w, n, K, ldw, gamma, beta, bias_in, wo, ldo, bias_out, colsum,
+                  threadIdx.x & 63);
+}
+
+// Every fold job of a model in one launch: blockIdx.y is the job of a device table, blockIdx.x
+// four of its rows; workgroups past a job's N leave (the grid is sized for the largest job).
+template <typename TO>
+__global__ __launch_bounds__(256) void fold_ln_batch_kernel(const vtd_fold_job* __restrict__ jobs) {
+  const vtd_fold_job j = jobs[blockIdx.y];
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= j.N) return;
+  fold_ln_row<TO>(j.w32, n, j.K, j.ldw, j.gamma, j.beta, j.bias_in, static_cast<TO*>(j.w_out),
+                  j.ldo, j.bias_out, j.colsum, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------ patches
@@ -1291,6 +1315,50 @@ int vtd_fold_layernorm(const float* w32_dev, int N, int K, int ldw, const float*
   return vtd::fold_ln_launch(w32_dev, N, K, ldw, gamma_dev, beta_dev, bias_in_dev, w_out_dev,
                              ldo, dtype, bias_out_dev, colsum_dev,
                              static_cast<hipStream_t>(stream));
+}
+
+int vtd_fold_plan_upload(const vtd_fold_job* jobs, int n_jobs, int dtype, void* plan_dev,
+                         size_t plan_bytes, int* max_rows, void* stream) {
+  VTD_CHECK_ARG(jobs && max_rows, "fold_plan_upload: null job table / max_rows");
+  VTD_CHECK_ARG(n_jobs > 0 && n_jobs <= 65535, "fold_plan_upload: n_jobs must be in [1, 65535]");
+  VTD_CHECK_ARG(dtype == VTD_F32 || dtype == VTD_BF16, "fold_plan_upload: bad dtype");
+  int most = 0;
+  for (int i = 0; i < n_jobs; ++i) {
+    const vtd_fold_job& j = jobs[i];
+    const std::string at = "fold_plan_upload: job " + std::to_string(i);
+    VTD_CHECK_ARG(j.w32 && j.gamma && j.beta && j.w_out && j.bias_out && j.colsum,
+                  at + ": null pointer");
+    VTD_CHECK_ARG(j.N > 0 && j.K > 0 && j.ldw >= j.K && j.ldo >= j.K, at + ": bad shape");
+    most = j.N > most ? j.N : most;
+  }
+  VTD_CHECK_ARG(plan_dev, "fold_plan_upload: null plan_dev");
+  VTD_CHECK_ARG(reinterpret_cast<uintptr_t>(plan_dev) % 16 == 0,
+                "fold_plan_upload: plan_dev needs a 16-B aligned base");
+  VTD_CHECK_ARG(plan_bytes >= (size_t)n_jobs * sizeof(vtd_fold_job),
+                "fold_plan_upload: plan_bytes too small");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  VTD_HIP(hipMemcpyAsync(plan_dev, jobs, (size_t)n_jobs * sizeof(vtd_fold_job),
+                         hipMemcpyHostToDevice, st));
+  VTD_HIP(hipStreamSynchronize(st));                 // the caller's table may go out of scope
+  *max_rows = most;
+  return VTD_OK;
+}
+
+int vtd_fold_layernorm_batch(const void* plan_dev, int n_jobs, int max_rows, int dtype,
+                             void* stream) {
+  VTD_CHECK_ARG(plan_dev, "fold_layernorm_batch: null plan_dev");
+  VTD_CHECK_ARG(n_jobs > 0 && n_jobs <= 65535 && max_rows > 0,
+                "fold_layernorm_batch: non-positive n_jobs / max_rows (n_jobs <= 65535)");
+  VTD_CHECK_ARG(dtype == VTD_F32 || dtype == VTD_BF16, "fold_layernorm_batch: bad dtype");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((max_rows + 3) / 4), (unsigned)n_jobs), block(256);
+  const vtd_fold_job* jobs = static_cast<const vtd_fold_job*>(plan_dev);
+  if (dtype == VTD_BF16)
+    hipLaunchKernelGGL(vtd::fold_ln_batch_kernel<vtd::bf16_t>, grid, block, 0, st, jobs);
+  else
+    hipLaunchKernelGGL(vtd::fold_ln_batch_kernel<float>, grid, block, 0, st, jobs);
+  VTD_LAUNCH_CHECK("fold_layernorm_batch");
+  return VTD_OK;
 }
 
 int vtd_extract_patches(const float* images_dev, int B, int H, int W, int C, int p,

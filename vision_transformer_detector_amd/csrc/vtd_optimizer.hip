@@ -1,6 +1,9 @@
 // Adam step of keras.optimizers.Adam (TF's ApplyAdam functor order) fused with the ClipWeight
 // constraint (vtd.py:209-236) and with the re-pack of the forward's operands: one launch per
 // training step over a table of tensors (vtd_adam_plan_upload, vtd_adam_step; include/vtd.h).
+// vtd_train_step ("whole-model step" below) is the same step over a table entry that also
+// carries vtd_pack_dense's grouping, a destination format, a constraint flag and an update rule
+// per tensor; the head's entries and their kernel are as they were.
 //
 // This file is compiled with -ffp-contract=off (Makefile) and with hipcc's correctly rounded
 // fp32 sqrt and division: every operation below is one IEEE fp32 operation, in the order
@@ -183,7 +186,219 @@ __global__ __launch_bounds__(kThreads) void adam_step_kernel(const AdamDesc* __r
   }
 }
 
+// ------------------------------------------------------------------ whole-model step
+// vtd_train_step: the same tile, thread ownership and LDS tile as above over vtd_train_tensor.
+// What the grouped destinations change:
+//   - a tile is 64 PACKED columns k' (k0' a multiple of 64) by 64 KERAS columns n.  Tile row kk
+//     holds k' = k0' + kk; it is the image of k = (k' / k_group_p) k_group + k' % k_group_p when
+//     k' % k_group_p < k_group and k' / k_group_p < K / k_group, else a pad row that leaves zeros
+//     in LDS.  A phase-2 run of 8 k' that straddles a group's end (k_group 10, k_group_p 32:
+//     k' = 8 .. 15 is two real columns and six pads) therefore reads its zeros from LDS like any
+//     other value.  Without a destination k_group = k_group_p = K: the identity.
+//   - along N the tile stays in the Keras layout, so a phase-1 vector of V columns never meets a
+//     group boundary (N % V == 0 is all it needs); phase 2 maps column n to packed row
+//     row_offset + (n / n_group) n_group_p + n % n_group.  Pad rows and the rows of the other
+//     tensors that share the buffer are the image of no n: never written.
+// The LDS tile is float[64][65] indexed (kk, nn) exactly as above, phase 1 writes and phase 2
+// reads it with the same lane -> (row, column) maps, so the bank argument at the top of this
+// file holds unchanged.  An fp32 destination stores the 8 values of a run as two 16-B stores.
+struct TrainDesc {
+  float* w; float* m; float* v; const float* g;
+  void* packed;
+  int kind, K, N, ld;
+  int kp;        // piece width of a packed row (matrix); K without a destination
+  int ntn;       // tiles along N (matrix)
+  int vec;       // 4 / 2 / 1: columns per thread in phase 1
+  int pk;        // destination: 0 none, 1 bf16, 2 split-bf16 [hi | hi | lo], 3 fp32
+  int kg, kgp, ng, ngp, off;
+  int constrain, rule;
+  int pad_;
+};
+
+// one element under the tensor's rule and constraint flag; returns the new w
+__device__ __forceinline__ float train_element(float w, float& m, float& v, float g,
+                                               const AdamScalars& s, int rule, int constrain) {
+  if (rule == VTD_TRAIN_RULE_DENSE) {
+    AdamScalars t = s;
+    t.constrain = s.constrain && constrain;
+    return adam_element(w, m, v, g, t);
+  }
+  if (s.clipvalue > 0.f) g = clip(g, -s.clipvalue, s.clipvalue);
+  const float omb1 = 1.f - s.beta1, omb2 = 1.f - s.beta2;
+  m = m * s.beta1 + g * omb1;
+  v = v * s.beta2 + (g * g) * omb2;
+  w = w - (s.alpha * m) / (sqrtf(v) + s.epsilon);
+  if (s.constrain && constrain) w = clip(w != w ? 1.f : w, -s.max_weight, s.max_weight);
+  return w;
+}
+
+template <int V>
+__device__ __forceinline__ void train_phase1(const TrainDesc& d, const AdamScalars& s, int k0,
+                                             int n0, float (*tile)[kPitch]) {
+  typedef float vecf __attribute__((ext_vector_type(V)));
+  const gptr<float> pw = as_global(d.w), pm = as_global(d.m), pv = as_global(d.v);
+  const gptr<const float> pg = as_global(d.g);
+  constexpr int kTpr = kTile / V;                  // threads per tile row
+  constexpr int kRpp = kThreads / kTpr;            // rows per pass
+  const int c = (threadIdx.x % kTpr) * V, r = threadIdx.x / kTpr;
+  const int groups = d.K / d.kg;
+#pragma unroll 2
+  for (int p = 0; p < kTile / kRpp; ++p) {
+    const int kk = p * kRpp + r, kq = k0 + kk, n = n0 + c;
+    const int grp = kq / d.kgp, in = kq - grp * d.kgp;
+    const int k = grp * d.kg + in;                 // used only when the row is real
+    float out[V];
+    if (in < d.kg && grp < groups && n < d.N) {    // N % V == 0: all V columns or none
+      const int64_t at = (int64_t)k * d.N + n;
+      float wv[V], mv[V], vv[V], gv[V];
+      if constexpr (V == 1) {
+        wv[0] = pw[at]; mv[0] = pm[at]; vv[0] = pv[at]; gv[0] = pg[at];
+      } else {
+        const vecf a = *(gptr<const vecf>)(pw + at);
+        const vecf b = *(gptr<const vecf>)(pm + at);
+        const vecf e = *(gptr<const vecf>)(pv + at);
+        const vecf f = *(gptr<const vecf>)(pg + at);
+#pragma unroll
+        for (int j = 0; j < V; ++j) { wv[j] = a[j]; mv[j] = b[j]; vv[j] = e[j]; gv[j] = f[j]; }
+      }
+#pragma unroll
+      for (int j = 0; j < V; ++j)
+        out[j] = train_element(wv[j], mv[j], vv[j], gv[j], s, d.rule, d.constrain);
+      if constexpr (V == 1) {
+        pw[at] = out[0]; pm[at] = mv[0]; pv[at] = vv[0];
+      } else {
+        vecf a, b, e;
+#pragma unroll
+        for (int j = 0; j < V; ++j) { a[j] = out[j]; b[j] = mv[j]; e[j] = vv[j]; }
+        *(gptr<vecf>)(pw + at) = a;
+        *(gptr<vecf>)(pm + at) = b;
+        *(gptr<vecf>)(pv + at) = e;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < V; ++j) out[j] = 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) tile[kk][c + j] = out[j];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void train_step_kernel(const TrainDesc* __restrict__ descs,
+                                                             const int2* __restrict__ map,
+                                                             AdamScalars s) {
+  __shared__ float tile[kTile][kPitch];
+  const int2 where = map[blockIdx.x];
+  const TrainDesc d = descs[where.x];
+  if (d.kind == VTD_ADAM_VECTOR) {
+    const int n = where.y * kVecTile + threadIdx.x;
+    if (n < d.N) {
+      const gptr<float> pw = as_global(d.w), pm = as_global(d.m), pv = as_global(d.v);
+      float m = pm[n], v = pv[n];
+      const float w = train_element(pw[n], m, v, as_global(d.g)[n], s, d.rule, d.constrain);
+      pw[n] = w; pm[n] = m; pv[n] = v;
+      if (d.packed)
+        as_global(static_cast<float*>(d.packed))[d.off + (n / d.ng) * d.ngp + n % d.ng] = w;
+    }
+    return;
+  }
+  const int k0 = (where.y / d.ntn) * kTile, n0 = (where.y % d.ntn) * kTile;
+  if (d.vec == 4) train_phase1<4>(d, s, k0, n0, tile);
+  else if (d.vec == 2) train_phase1<2>(d, s, k0, n0, tile);
+  else train_phase1<1>(d, s, k0, n0, tile);
+  if (!d.packed) return;                            // uniform per workgroup
+  __syncthreads();
+  const int kc = k0 + 8 * (threadIdx.x & 7);
+#pragma unroll
+  for (int p = 0; p < kTile / (kThreads / 8); ++p) {
+    const int nn = p * (kThreads / 8) + (threadIdx.x >> 3), n = n0 + nn;
+    if (n >= d.N || kc >= d.kp) continue;           // kp % 8 == 0: all 8 or none
+    const int64_t prow = (int64_t)d.off + (n / d.ng) * d.ngp + n % d.ng;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = tile[kc - k0 + j][nn];
+    if (d.pk == 3) {                                // fp32 staging [N_p][K_p]
+      const gptr<float> row = as_global(static_cast<float*>(d.packed)) + prow * d.ld + kc;
+      *(gptr<f32x4>)row = f32x4{v[0], v[1], v[2], v[3]};
+      *(gptr<f32x4>)(row + 4) = f32x4{v[4], v[5], v[6], v[7]};
+      continue;
+    }
+    const uint32_t h0 = pack_bf16x2(v[0], v[1]), h1 = pack_bf16x2(v[2], v[3]),
+                   h2 = pack_bf16x2(v[4], v[5]), h3 = pack_bf16x2(v[6], v[7]);
+    const i32x4 hi = {(int)h0, (int)h1, (int)h2, (int)h3};
+    const gptr<bf16_t> row = as_global(static_cast<bf16_t*>(d.packed)) + prow * d.ld + kc;
+    *(gptr<i32x4>)row = hi;
+    if (d.pk == 2) {                                // B operand [hi | hi | lo]
+      const i32x4 lo = {(int)pack_lo_bf16x2(v[0], v[1], h0), (int)pack_lo_bf16x2(v[2], v[3], h1),
+                        (int)pack_lo_bf16x2(v[4], v[5], h2), (int)pack_lo_bf16x2(v[6], v[7], h3)};
+      *(gptr<i32x4>)(row + d.kp) = hi;
+      *(gptr<i32x4>)(row + 2 * d.kp) = lo;
+    }
+  }
+}
+
 // ------------------------------------------------------------------ plan (host)
+int check_train_tensors(const vtd_train_tensor* t, int n, int dtype, const char* what) {
+  const std::string w(what);
+  VTD_CHECK_ARG(t, w + ": null tensor table");
+  VTD_CHECK_ARG(n > 0, w + ": n_tensors must be positive");
+  for (int i = 0; i < n; ++i) {
+    const vtd_train_tensor& a = t[i];
+    const std::string at = w + ": tensor " + std::to_string(i);
+    VTD_CHECK_ARG(a.w && a.m && a.v && a.g, at + ": null pointer (w, m, v, g)");
+    VTD_CHECK_ARG(a.kind == VTD_ADAM_MATRIX || a.kind == VTD_ADAM_VECTOR, at + ": bad kind");
+    VTD_CHECK_ARG(a.N > 0 && (a.kind == VTD_ADAM_VECTOR || a.K > 0),
+                  at + ": non-positive size");
+    for (const void* p : {(const void*)a.w, (const void*)a.m, (const void*)a.v,
+                          (const void*)a.g})
+      VTD_CHECK_ARG(reinterpret_cast<uintptr_t>(p) % 16 == 0, at + ": w, m, v, g need 16-B "
+                    "aligned bases");
+    VTD_CHECK_ARG(a.rule == VTD_TRAIN_RULE_DENSE || a.rule == VTD_TRAIN_RULE_SPARSE,
+                  at + ": bad rule");
+    VTD_CHECK_ARG(a.packed_dtype == VTD_TRAIN_PACK_NONE || a.packed_dtype == VTD_TRAIN_PACK_MODE ||
+                  a.packed_dtype == VTD_TRAIN_PACK_F32, at + ": bad packed_dtype");
+    VTD_CHECK_ARG((a.packed_dtype == VTD_TRAIN_PACK_NONE) == (a.packed == nullptr),
+                  at + ": packed_dtype NONE goes with a null destination and only with one");
+    if (!a.packed) continue;
+    VTD_CHECK_ARG(a.packed_dtype != VTD_TRAIN_PACK_MODE || dtype == VTD_BF16 ||
+                  dtype == VTD_BF16X3,
+                  at + ": a destination in the mode's format needs dtype VTD_BF16 or VTD_BF16X3");
+    VTD_CHECK_ARG(a.n_group > 0 && a.n_group_p >= a.n_group && a.N % a.n_group == 0,
+                  at + ": bad n group (n_group > 0, n_group_p >= n_group, N % n_group == 0)");
+    VTD_CHECK_ARG(a.row_offset >= 0, at + ": negative row_offset");
+    if (a.kind == VTD_ADAM_VECTOR) {                  // fp32, ld and the k groups unused
+      VTD_CHECK_ARG(reinterpret_cast<uintptr_t>(a.packed) % 4 == 0,
+                    at + ": a vector's destination needs a 4-B aligned base");
+      continue;
+    }
+    VTD_CHECK_ARG(a.k_group > 0 && a.k_group_p >= a.k_group && a.K % a.k_group == 0,
+                  at + ": bad k group (k_group > 0, k_group_p >= k_group, K % k_group == 0)");
+    const bool x3 = a.packed_dtype == VTD_TRAIN_PACK_MODE && dtype == VTD_BF16X3;
+    VTD_CHECK_ARG(!x3 || a.ld % 3 == 0,
+                  at + ": ld must be a multiple of 3 in split-bf16 (ld = 3 K_p)");
+    const int64_t kp = x3 ? a.ld / 3 : a.ld;
+    const int64_t last = (int64_t)(a.K / a.k_group - 1) * a.k_group_p + a.k_group;
+    VTD_CHECK_ARG(kp >= last, at + ": ld too small (K_p < the last packed column + 1)");
+    VTD_CHECK_ARG(kp % 8 == 0 && reinterpret_cast<uintptr_t>(a.packed) % 16 == 0,
+                  at + ": packed rows are written 16 B at a time: K_p % 8 == 0 and a 16-B "
+                  "aligned base");
+  }
+  return VTD_OK;
+}
+
+int train_tensor_tiles(const vtd_train_tensor& a, int dtype, int* ntn, int* kp_out) {
+  if (a.kind == VTD_ADAM_VECTOR) { *ntn = 1; *kp_out = 0; return (a.N + kVecTile - 1) / kVecTile; }
+  // with a destination the K tiles run over the packed columns to K_p, so that every pad is zeroed
+  const bool x3 = a.packed_dtype == VTD_TRAIN_PACK_MODE && dtype == VTD_BF16X3;
+  const int kp = a.packed ? (x3 ? a.ld / 3 : a.ld) : a.K;
+  *ntn = (a.N + kTile - 1) / kTile;
+  *kp_out = kp;
+  return ((kp + kTile - 1) / kTile) * *ntn;
+}
+
+size_t train_plan_bytes(int n, int64_t tiles) {
+  return (size_t)round_up((int64_t)n * sizeof(TrainDesc), 16) + (size_t)tiles * sizeof(int2);
+}
+
 int check_tensors(const vtd_adam_tensor* t, int n, int dtype, const char* what) {
   const std::string w(what);
   VTD_CHECK_ARG(t, w + ": null tensor table");
@@ -301,6 +516,87 @@ int vtd_adam_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
   hipLaunchKernelGGL(vtd::adam_step_kernel, dim3((unsigned)tiles), dim3(vtd::kThreads), 0, st,
                      reinterpret_cast<const vtd::AdamDesc*>(base), map, s);
   VTD_LAUNCH_CHECK("adam_step");
+  return VTD_OK;
+}
+
+int vtd_train_plan_bytes(const vtd_train_tensor* tensors, int n_tensors, int dtype, size_t* bytes,
+                         int* tiles) {
+  VTD_CHECK_ARG(bytes && tiles, "train_plan_bytes: null output");
+  if (int rc = vtd::check_train_tensors(tensors, n_tensors, dtype, "train_plan_bytes")) return rc;
+  int64_t total = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    int ntn, kp;
+    total += vtd::train_tensor_tiles(tensors[i], dtype, &ntn, &kp);
+  }
+  VTD_CHECK_ARG(total <= 0x7fffffff, "train_plan_bytes: too many tiles");
+  *tiles = (int)total;
+  *bytes = vtd::train_plan_bytes(n_tensors, total);
+  return VTD_OK;
+}
+
+int vtd_train_plan_upload(const vtd_train_tensor* tensors, int n_tensors, int dtype,
+                          void* plan_dev, size_t plan_bytes, void* stream) {
+  size_t need = 0;
+  int tiles = 0;
+  if (int rc = vtd_train_plan_bytes(tensors, n_tensors, dtype, &need, &tiles)) return rc;
+  VTD_CHECK_ARG(plan_dev, "train_plan_upload: null plan_dev");
+  VTD_CHECK_ARG(reinterpret_cast<uintptr_t>(plan_dev) % 16 == 0,
+                "train_plan_upload: plan_dev needs a 16-B aligned base");
+  VTD_CHECK_ARG(plan_bytes >= need, "train_plan_upload: plan_bytes too small");
+  std::vector<char> host(need, 0);
+  vtd::TrainDesc* d = reinterpret_cast<vtd::TrainDesc*>(host.data());
+  int2* map = reinterpret_cast<int2*>(
+      host.data() + vtd::round_up((int64_t)n_tensors * sizeof(vtd::TrainDesc), 16));
+  int at = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const vtd_train_tensor& a = tensors[i];
+    const bool matrix = a.kind == VTD_ADAM_MATRIX;
+    int ntn, kp;
+    const int nt = vtd::train_tensor_tiles(a, dtype, &ntn, &kp);
+    d[i].w = a.w; d[i].m = a.m; d[i].v = a.v; d[i].g = a.g; d[i].packed = a.packed;
+    d[i].kind = a.kind; d[i].K = matrix ? a.K : 1; d[i].N = a.N;
+    d[i].ld = a.ld; d[i].kp = kp; d[i].ntn = ntn;
+    d[i].vec = a.N % 4 == 0 ? 4 : (a.N % 2 == 0 ? 2 : 1);
+    d[i].pk = !a.packed ? 0 : a.packed_dtype == VTD_TRAIN_PACK_F32 ? 3
+                              : dtype == VTD_BF16X3 ? 2 : 1;
+    // without a destination the packed column is the Keras one
+    d[i].kg = a.packed && matrix ? a.k_group : d[i].K;
+    d[i].kgp = a.packed && matrix ? a.k_group_p : d[i].K;
+    d[i].ng = a.packed ? a.n_group : a.N;
+    d[i].ngp = a.packed ? a.n_group_p : a.N;
+    d[i].off = a.packed ? a.row_offset : 0;
+    d[i].constrain = a.constrain ? 1 : 0; d[i].rule = a.rule;
+    for (int t = 0; t < nt; ++t) map[at++] = int2{i, t};
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  VTD_HIP(hipMemcpyAsync(plan_dev, host.data(), need, hipMemcpyHostToDevice, st));
+  VTD_HIP(hipStreamSynchronize(st));                 // `host` goes out of scope
+  return VTD_OK;
+}
+
+int vtd_train_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
+                   double learning_rate, float beta1, float beta2, float epsilon, float clipvalue,
+                   int constrain, float max_weight, void* stream) {
+  VTD_CHECK_ARG(plan_dev, "train_step: null plan_dev");
+  VTD_CHECK_ARG(n_tensors > 0 && tiles > 0, "train_step: non-positive n_tensors / tiles");
+  VTD_CHECK_ARG(t >= 1, "train_step: t (the step number) starts at 1");
+  VTD_CHECK_ARG(!constrain || max_weight > 0.f, "train_step: max_weight must be positive");
+  // alpha as in vtd_adam_step: in double from the fp32 betas, rounded once
+  const double b1 = beta1, b2 = beta2;
+  vtd::AdamScalars s;
+  s.alpha = (float)(learning_rate * std::sqrt(1.0 - std::pow(b2, (double)t)) /
+                    (1.0 - std::pow(b1, (double)t)));
+  s.beta1 = beta1; s.beta2 = beta2; s.epsilon = epsilon;
+  s.clipvalue = clipvalue > 0.f ? clipvalue : 0.f;
+  s.max_weight = max_weight; s.constrain = constrain ? 1 : 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  vtd::ProfScope ps(st, vtd::PROF_OTHER, 0.0);
+  const char* base = static_cast<const char*>(plan_dev);
+  const int2* map = reinterpret_cast<const int2*>(
+      base + vtd::round_up((int64_t)n_tensors * sizeof(vtd::TrainDesc), 16));
+  hipLaunchKernelGGL(vtd::train_step_kernel, dim3((unsigned)tiles), dim3(vtd::kThreads), 0, st,
+                     reinterpret_cast<const vtd::TrainDesc*>(base), map, s);
+  VTD_LAUNCH_CHECK("train_step");
   return VTD_OK;
 }
 

@@ -160,6 +160,7 @@ class Model:
         self.metrics = []
         self.optimizer = None          # compile(): stored as given, resolved by a training call
         self._head_dirty = False       # the head's device masters are ahead of self._master
+        self._enc_dirty = False        # so are the encoder's and the stem's (train_on_batch)
         self.set_weights(keras_default_init(self.weight_shapes, seed))
 
     # ---- config helpers
@@ -186,8 +187,13 @@ class Model:
         return list(self.weight_shapes)
 
     def _sync_master(self):
-        """After optimizer steps the head's device masters are the truth: read them back into
-        the fp32 CPU masters (once per run of steps; the encoder's entries are untouched)."""
+        """After optimizer steps the device masters are the truth -- the head's after head-only
+        steps, every tensor's after all-weights steps: read back what is dirty into the fp32 CPU
+        masters (once per run of steps)."""
+        if self._enc_dirty:               # an all-weights step: the encoder and the stem too
+            for n, t in self._encoder_master().items():
+                self._master[n] = t.cpu()
+            self._enc_dirty = False
         if self._head_dirty:
             for n, t in self._head_master().items():
                 self._master[n] = t.cpu()
@@ -219,7 +225,7 @@ class Model:
                                  f"{self.weight_shapes[n]}")
             master[n] = t.contiguous()
         self._master = master
-        self._head_dirty = False
+        self._head_dirty = self._enc_dirty = False
         self._pack()
         if hasattr(self.optimizer, "_reset"):       # its table points at the old device masters
             self.optimizer._reset(self)
@@ -263,6 +269,14 @@ class Model:
         dev = self.device
         keep, staging = [], []
         head = {}        # Keras name -> packed tensor of the head (vtd_adam_step re-packs them)
+        # Keras name -> where the forward's copy of that tensor lives (vtd_train_step re-packs
+        # it): the packed tensor `t` and vtd_pack_dense's / vtd_pack_vector's grouping, or
+        # `fold`: the index in `folds` of the LayerNorm fold job whose fp32 staging operand it
+        # belongs to.  Not filled for the MX-fp8 layers (no training in that mode).
+        train, folds = {}, []
+
+        def rec(name, t=None, fold=None, kg=None, kgp=None, ng=None, ngp=None, off=0):
+            train[name] = dict(t=t, fold=fold, kg=kg, kgp=kgp, ng=ng, ngp=ngp, off=off)
         stream = L.stream_ptr(torch.cuda.current_stream(dev))
 
         def zeros(*shape, dtype=tdt):
@@ -320,7 +334,9 @@ class Model:
             """Encoder Dense layer: packed in the compute dtype, or MX-fp8 in FP8 mode.
             Returns (matrix pointer, scale pointer or None)."""
             if not fp8:
-                return dense(name, rows_p, k_p, **kw).data_ptr(), None
+                t = dense(name, rows_p, k_p, **kw)
+                rec(name + "/kernel", t, kg=kw.get("kg"), kgp=kw.get("kgp"))
+                return t.data_ptr(), None
             return mx8(dense(name, rows_p, k_p, dst=f32_staging(rows_p, k_p), pdt=L.F32, **kw),
                        name)
 
@@ -333,7 +349,8 @@ class Model:
                 and os.environ.get("VTD_RESID_F32", "0") in ("", "0"))
 
         def fold_ln(w32, b32, gamma, beta):
-            """(W * diag(gamma), b + W beta, colsum) of a packed fp32 [N_p][K_p] matrix."""
+            """(W * diag(gamma), b + W beta, colsum) of a packed fp32 [N_p][K_p] matrix; the
+            job is kept in `folds` for the refresh after an optimizer step."""
             n_p, k_p = w32.shape
             wo = zeros(n_p, k_p)
             bo = zeros(n_p, dtype=torch.float32)
@@ -342,6 +359,8 @@ class Model:
                                              beta.data_ptr(), b32.data_ptr(), wo.data_ptr(),
                                              k_p, dt, bo.data_ptr(), cs.data_ptr(), stream),
                     "fold_layernorm")
+            folds.append(dict(shape=(n_p, k_p), gamma=gamma, beta=beta, bias_in=b32, wo=wo,
+                              bo=bo, cs=cs))
             return wo.data_ptr(), bo.data_ptr(), cs.data_ptr()
 
         def vector(name, n_p, ng=None, ngp=None, dst=None, off=0):
@@ -356,10 +375,13 @@ class Model:
         kw = self.kwargs
         dk, dkp = kw["encoder_key_dim"], dims.key_dim_p
         W = L.VtdWeights()
-        W.w_patch = dense("linear_projection", dims.d_p, dims.patch_dim_p).data_ptr()
-        W.b_patch = vector("linear_projection/bias", dims.d_p).data_ptr()
+        rec("linear_projection/kernel", dense("linear_projection", dims.d_p, dims.patch_dim_p))
+        rec("linear_projection/bias", vector("linear_projection/bias", dims.d_p))
+        W.w_patch = train["linear_projection/kernel"]["t"].data_ptr()
+        W.b_patch = train["linear_projection/bias"]["t"].data_ptr()
         pos = src("position_encoding/position_embedding/embeddings").reshape(-1)
         keep.append(pos)
+        rec("position_encoding/position_embedding/embeddings", pos)
         W.pos_embedding = pos.data_ptr()
         nl = kw["encoder_repeat_times"]
         layers = (L.VtdLayerWeights * nl)()
@@ -372,6 +394,9 @@ class Model:
             g2, b2 = vector(f"{ln2}/gamma", dims.d_p), vector(f"{ln2}/beta", dims.d_p)
             Ly.ln1_gamma, Ly.ln1_beta = g1.data_ptr(), b1.data_ptr()
             Ly.ln2_gamma, Ly.ln2_beta = g2.data_ptr(), b2.data_ptr()
+            for n, t in ((f"{ln1}/gamma", g1), (f"{ln1}/beta", b1), (f"{ln2}/gamma", g2),
+                         (f"{ln2}/beta", b2)):
+                rec(n, t)
             wqkv = (f32_staging(dims.qkv_p, dims.d_p) if fp8 or fold or x3
                     else zeros(dims.qkv_p, dims.d_p))
             bqkv = zeros(dims.qkv_p, dtype=torch.float32)
@@ -381,23 +406,32 @@ class Model:
                 dense(f"{mha}/{part}", None, dims.d_p, ng=dk, ngp=dkp, dst=wqkv, off=off,
                       pdt=L.F32 if fp8 or fold or x3 else None)
                 vector(f"{mha}/{part}/bias", None, ng=dk, ngp=dkp, dst=bqkv, off=off)
+            wqkv_op = None if fp8 or fold else split3(wqkv) if x3 else wqkv
             Ly.w_qkv, Ly.s_qkv = (mx8(wqkv, f"{mha}/qkv") if fp8 else
-                                  (split3(wqkv).data_ptr(), None) if x3 else
-                                  (wqkv.data_ptr(), None))
+                                  (wqkv.data_ptr() if fold else wqkv_op.data_ptr(), None))
             Ly.b_qkv = bqkv.data_ptr()
             if fold:
                 Ly.w_qkv, Ly.b_qkv, Ly.ln1_colsum = fold_ln(wqkv, bqkv, g1, b1)
+            for part_i, part in enumerate(("query", "key", "value")):
+                off = part_i * dims.inner_p
+                if not fp8:
+                    rec(f"{mha}/{part}/kernel", wqkv_op, fold=len(folds) - 1 if fold else None,
+                        ng=dk, ngp=dkp, off=off)
+                rec(f"{mha}/{part}/bias", bqkv, ng=dk, ngp=dkp, off=off)
             # attention_output kernel (H, dk, D) -> (H*dk, D); rows padded per head
             Ly.w_out, Ly.s_out = enc(f"{mha}/attention_output", dims.d_p, dims.inner_p, kg=dk,
                                      kgp=dkp)
-            Ly.b_out = vector(f"{mha}/attention_output/bias", dims.d_p).data_ptr()
+            rec(f"{mha}/attention_output/bias", vector(f"{mha}/attention_output/bias", dims.d_p))
+            Ly.b_out = train[f"{mha}/attention_output/bias"]["t"].data_ptr()
             k_p = dims.d_p
             for j in range(kw["encoder_mlp_quantities"]):
                 n_p = dims.mlp_units_p[j]
                 bm = vector(f"MLP_{i}_{j + 1}/bias", n_p)
+                rec(f"MLP_{i}_{j + 1}/bias", bm)
                 if fold and j == 0:
                     w32 = dense(f"MLP_{i}_{j + 1}", n_p, k_p, dst=f32_staging(n_p, k_p), pdt=L.F32)
                     Ly.w_mlp[j], Ly.b_mlp[j], Ly.ln2_colsum = fold_ln(w32, bm, g2, b2)
+                    rec(f"MLP_{i}_{j + 1}/kernel", fold=len(folds) - 1)
                 else:
                     Ly.w_mlp[j], Ly.s_mlp[j] = enc(f"MLP_{i}_{j + 1}", n_p, k_p)
                     Ly.b_mlp[j] = bm.data_ptr()
@@ -422,6 +456,9 @@ class Model:
         del staging      # fp32 staging copies; the packed buffers stay alive in `keep`
         self._packed = keep
         self._head_packed = head
+        for n, t in head.items():
+            rec(n, t)
+        self._train_packed, self._fold_jobs = train, folds
         self._layers_c = layers
         self._weights_c = W
 
@@ -487,8 +524,8 @@ class Model:
     def compile(self, optimizer=None, loss=None, metrics=None, **_):
         """keras.Model.compile: stores `optimizer`, `loss` and `metrics`.  `optimizer` is kept as
         given and never refused here -- optimizers.Adam or the string "adam" (= Adam()) train the
-        head (train_head_on_batch, fit_head); anything else raises only when a training call
-        needs it.  `loss` is my_custom_loss or a
+        head (train_head_on_batch, fit_head) or every weight (train_on_batch, fit); anything
+        else raises only when a training call needs it.  `loss` is my_custom_loss or a
         functools.partial of it (its keywords are read off and evaluate runs the fused
         from-logits kernel), or any callable (y_true, logits) -> scalar, called per batch.
         `metrics`: objects with update_state / result / reset_state (MeanAveragePrecision)."""
@@ -617,6 +654,14 @@ class Model:
                              f"[0, {reps})")
         per = 12 + 2 * self.kwargs["encoder_mlp_quantities"]
         names = list(self.weight_shapes)[3 + i * per: 3 + (i + 1) * per]
+        return self._current(names)
+
+    def _current(self, names):
+        """Fresh device copies of encoder / stem weights: of the device masters where optimizer
+        steps have moved them ahead of the CPU masters, else of the CPU masters."""
+        if self._enc_dirty:
+            live = self._encoder_master()
+            return OrderedDict((n, live[n].clone()) for n in names)
         return OrderedDict((n, self._master[n].to(self.device).contiguous()) for n in names)
 
     def _head_master(self):
@@ -646,8 +691,7 @@ class Model:
         Keras name -> fp32 device tensor in the Keras shape, in creation order (the position
         embedding (tokens, 1), the linear_projection kernel and bias).  Fresh copies of the
         model's current weights, as `encoder_block_weights` returns a block's."""
-        names = list(self.weight_shapes)[:3]
-        return OrderedDict((n, self._master[n].to(self.device).contiguous()) for n in names)
+        return self._current(list(self.weight_shapes)[:3])
 
     def _encoder_master(self):
         """fp32 device copies of the stem's and every encoder block's weights in the Keras
@@ -675,12 +719,18 @@ class Model:
         head_gradients' pass on the last block's output, then the blocks' backward calls in
         reverse through one shared workspace and the stem's.  Needs compile(loss=my_custom_loss
         or a functools.partial of it) and dtype 'bf16x3' or 'bfloat16'."""
+        return self._grad_chain("gradients", images, y_true)
+
+    def _grad_chain(self, what, images, y_true, buffers=None):
+        """The chain gradients and train_on_batch share.  `buffers`: Keras name -> fp32 device
+        tensor to write each weight gradient into (the optimizer's persistent ones); None
+        allocates fresh tensors.  Returns (out5, grads keyed by `weight_names()`)."""
         if self.dtype not in (L.BF16X3, L.BF16):
-            raise ValueError("gradients: the head backward runs in the 'bf16x3' and "
+            raise ValueError(f"{what}: the head backward runs in the 'bf16x3' and "
                              "'bfloat16' modes only (not float32 / float8)")
         from . import loss as _loss
         if self.loss is None or _loss.fused_loss_params(self.loss) is None:
-            raise ValueError("gradients: compile(loss=my_custom_loss or a functools.partial "
+            raise ValueError(f"{what}: compile(loss=my_custom_loss or a functools.partial "
                              "of it with keyword arguments) first")
         from . import encoder as _enc
         from . import stem as _stem
@@ -709,15 +759,106 @@ class Model:
             xs = [_stem.run(x, sw, sdims, ws=stem_ws)[0]]
             for i in range(reps):
                 xs.append(_enc.run(xs[i], bw[i], bdims, ws=block_ws)[0])
-            out5, head = self._head_pass("gradients", None, y_true, xs[reps])
+            names = list(self.weight_shapes)
+            into = None if buffers is None else [buffers[n] for n in names]
+            head_into = None
+            if into is not None:
+                head_into = OrderedDict(zip(names[3 + reps * per:], into[3 + reps * per:]))
+                head_into["encoded_images"] = torch.empty_like(xs[reps])
+            out5, head = self._head_pass(what, None, y_true, xs[reps], weight_grads=head_into)
+            head = OrderedDict(head)
             dy = head.pop("encoded_images")
             found = []
             for i in range(reps - 1, -1, -1):
-                _, g, dy = _enc.run(xs[i], bw[i], bdims, dy=dy, want_y=False, ws=block_ws)
+                out = None if into is None else (None, into[3 + i * per: 3 + (i + 1) * per], None)
+                _, g, dy = _enc.run(xs[i], bw[i], bdims, dy=dy, want_y=False, ws=block_ws,
+                                    out=out)
                 found = g + found
-            _, g = _stem.run(x, sw, sdims, dx0=dy, want_x0=False, ws=stem_ws)
+            _, g = _stem.run(x, sw, sdims, dx0=dy, want_x0=False, ws=stem_ws,
+                             out=None if into is None else (None, into[:3]))
             found = g + found + list(head.values())
         return out5, OrderedDict(zip(self.weight_shapes, found))
+
+    # ---- whole-model training (vtd_train_step, vtd_fold_layernorm_batch; optimizers.py)
+    def _training_optimizer(self, what):
+        if self.dtype not in (L.BF16X3, L.BF16):
+            raise ValueError(f"{what}: the model trains in the 'bf16x3' and 'bfloat16' modes "
+                             "only (not float32 / float8)")
+        if self.kwargs.get("dropout"):
+            raise ValueError(f"{what}: the training graph here is the dropout=None graph; this "
+                             f"model was built with dropout={self.kwargs['dropout']!r}")
+        from . import loss as _loss
+        if self.loss is None or _loss.fused_loss_params(self.loss) is None:
+            raise ValueError(f"{what}: compile(loss=my_custom_loss or a functools.partial "
+                             "of it with keyword arguments) first")
+        from . import optimizers as _opt
+        try:
+            return _opt.resolve(self.optimizer)
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+
+    def train_on_batch(self, images, y_true):
+        """keras.Model.train_on_batch over every weight: gradients' chain with each weight
+        gradient written into the compiled optimizer's persistent buffers, then ONE
+        vtd_train_step launch -- Adam (the position embedding in Keras's sparse-path order and
+        without the constraint, as the reference builds it), ClipWeight (`max_weight` /
+        `clip_weight` of the model's kwargs) and the re-pack of every operand the inference
+        forward reads -- and, where the model was packed with the LayerNorm fold, one
+        vtd_fold_layernorm_batch launch that refreshes the folded operands.  Returns out5 as
+        gradients does, taken before the update, as Keras reports the loss; nothing is read
+        back.  Afterwards the device masters are the truth for every tensor; get_weights /
+        get_weight_dict / save_weights read them back on demand.  Needs
+        compile(optimizer=optimizers.Adam(...) or 'adam', loss=my_custom_loss or a
+        functools.partial of it), dtype 'bf16x3' or 'bfloat16' and a model without dropout."""
+        optimizer = self._training_optimizer("train_on_batch")
+        out5, _ = self._grad_chain("train_on_batch", images, y_true,
+                                   optimizer.gradient_buffers(self, scope="all"))
+        optimizer.apply(self, scope="all")
+        return out5
+
+    def fit(self, x, y=None, batch_size=32, epochs=1, lr_schedule=None, callbacks=None,
+            verbose=0):
+        """keras.Model.fit over every weight: `epochs` passes of train_on_batch over the
+        batches, formed as `evaluate` forms them (arrays split by `batch_size`, the last may be
+        short; or y=None and `x` a re-iterable of (images, labels) batches).  `lr_schedule(epoch,
+        lr) -> lr` is called at the start of every epoch, as keras.callbacks.
+        LearningRateScheduler calls it.  `callbacks`: a list of objects; `set_model(model)` is
+        called once on those that have it, `on_epoch_end(epoch, {"loss": ...})` after every
+        epoch (no other Keras hook is called).  Returns an object whose .history["loss"] holds
+        one float per epoch: the mean of the batch losses weighted by batch size, accumulated
+        on the device and read once per epoch."""
+        del verbose
+        from . import optimizers as _opt
+        from .metrics import _device_f32
+        optimizer = self._training_optimizer("fit")
+        if int(epochs) < 0:
+            raise ValueError(f"fit: epochs must be >= 0, got {epochs}")
+        callbacks = list(callbacks or [])
+        for cb in callbacks:
+            if callable(getattr(cb, "set_model", None)):
+                cb.set_model(self)
+        hist = _opt.History()
+        with torch.cuda.device(self.device):
+            running = torch.zeros(2, dtype=torch.float64, device=self.device)
+            for epoch in range(int(epochs)):
+                if lr_schedule is not None:
+                    optimizer.learning_rate = float(lr_schedule(epoch, optimizer.learning_rate))
+                running.zero_()
+                for images, labels in self._evaluate_batches(x, y, batch_size):
+                    n = len(labels)
+                    if n == 0:
+                        continue
+                    out5 = self.train_on_batch(images, _device_f32(labels, self.device))
+                    running[0] += out5[0].double() * n
+                    running[1] += n
+                total, count = running.cpu().tolist()       # the epoch's one host read
+                loss = total / count if count else float("nan")
+                hist.history["loss"].append(loss)
+                hist.epoch.append(epoch)
+                for cb in callbacks:
+                    if callable(getattr(cb, "on_epoch_end", None)):
+                        cb.on_epoch_end(epoch, {"loss": loss})
+        return hist
 
     # ---- head training (vtd_adam_step; optimizers.py)
     def train_head_on_batch(self, images, y_true, encoded=None):
@@ -740,8 +881,8 @@ class Model:
         except ValueError as e:
             raise ValueError(f"train_head_on_batch: {e}") from None
         out5, _ = self._head_pass("train_head_on_batch", images, y_true, encoded,
-                                  weight_grads=optimizer.gradient_buffers(self))
-        optimizer.apply(self)
+                                  weight_grads=optimizer.gradient_buffers(self, scope="head"))
+        optimizer.apply(self, scope="head")
         return out5
 
     def fit_head(self, x, y=None, batch_size=32, epochs=1, lr_schedule=None, cache_features=True,

@@ -5,6 +5,11 @@ and the step schedule `learning_rate_step_decay` (vtd.py:696-728).
 The update itself is one launch of vtd_adam_step per training step (csrc/vtd_optimizer.hip):
 Adam, the constraint and the re-pack of the forward's head operands, over a table of the
 head's tensors that is uploaded once.  There is no host arithmetic on the weights.
+
+The same optimizer trains every weight (Model.train_on_batch / fit, scope "all"): one launch of
+vtd_train_step over a table of all tensors, whose entries carry the grouping, destination format,
+constraint flag and update rule of each, then one launch of vtd_fold_layernorm_batch where the
+model's LayerNorms are folded into the next GEMM's operands.
 """
 from __future__ import annotations
 
@@ -60,51 +65,87 @@ class Adam:
             self._state = None
             self.iterations = 0
 
-    def _state_for(self, model):
+    _METHODS = {"head": "train_head_on_batch / fit_head", "all": "train_on_batch / fit"}
+
+    def _state_for(self, model, scope=None):
+        """The state of `model` in `scope`: "head" (the detection head on a frozen encoder) or
+        "all" (every weight); None keeps the scope of the state there is, "head" if none."""
         st = self._state
-        if st is None or st.model() is not model or st.master_of is not model._master:
+        fresh = st is None or st.model() is not model or st.master_of is not model._master
+        if scope is None:
+            scope = "head" if fresh else st.scope
+        if scope not in self._METHODS:
+            raise ValueError(f"Adam: scope must be 'head' or 'all', got {scope!r}")
+        if not fresh and st.scope != scope:
+            if self.iterations > 0:
+                raise ValueError(
+                    f"Adam: this optimizer has taken {self.iterations} step(s) with "
+                    f"{self._METHODS[st.scope]} (scope {st.scope!r}); its moments do not carry "
+                    f"over to {self._METHODS[scope]}: compile a new optimizer to switch")
+            fresh = True
+        if fresh:
             self.iterations = 0
-            st = self._state = _State(model)
+            st = self._state = _State(model, scope)
         return st
 
-    def gradient_buffers(self, model):
-        """The persistent fp32 gradient buffers of `model`'s head, keyed by Keras weight name:
-        what the next `apply` reads."""
-        return self._state_for(model).grads
+    def gradient_buffers(self, model, scope=None):
+        """The persistent fp32 gradient buffers of `model`, keyed by Keras weight name: what the
+        next `apply` reads -- the head's tensors or, in scope "all", every tensor of
+        `weight_names()`."""
+        return self._state_for(model, scope).grads
 
-    def moments(self, model):
-        """(m, v) as dicts of the live fp32 device tensors, keyed by Keras weight name."""
-        st = self._state_for(model)
+    def moments(self, model, scope=None):
+        """(m, v) as dicts of the live fp32 device tensors, keyed by Keras weight name, over
+        whatever the scope covers."""
+        st = self._state_for(model, scope)
         return st.m, st.v
 
-    def apply(self, model, stream=None):
-        """One step on `model`'s head from the gradient buffers: a single vtd_adam_step launch
-        that updates the device masters, the moments and the forward's packed operands."""
-        st = self._state_for(model)
+    def apply(self, model, stream=None, scope=None):
+        """One step on `model` from the gradient buffers.  Scope "head": a single vtd_adam_step
+        launch that updates the head's device masters, moments and packed operands.  Scope
+        "all": a single vtd_train_step launch over every weight and, where the model was packed
+        with the LayerNorm fold, one vtd_fold_layernorm_batch launch that refreshes the folded
+        operands from the staging the step wrote."""
+        st = self._state_for(model, scope)
         constrain = bool(model.kwargs.get("clip_weight", True))
         max_weight = float(model.kwargs.get("max_weight", 10) or 0.0)
         if constrain and not max_weight > 0.0:
             raise ValueError(f"Adam: clip_weight needs a positive max_weight, got "
                              f"{model.kwargs.get('max_weight')!r}")
+        step, what = ((L.lib.vtd_train_step, "vtd_train_step") if st.scope == "all" else
+                      (L.lib.vtd_adam_step, "vtd_adam_step"))
         with torch.cuda.device(model.device):
-            L.check(L.lib.vtd_adam_step(st.plan.data_ptr(), st.n, st.tiles, self.iterations + 1,
-                                        float(self.learning_rate), self.beta_1, self.beta_2,
-                                        self.epsilon, self.clipvalue or 0.0, int(constrain),
-                                        max_weight if constrain else 0.0,
-                                        L.stream_ptr(stream)), "vtd_adam_step")
+            L.check(step(st.plan.data_ptr(), st.n, st.tiles, self.iterations + 1,
+                         float(self.learning_rate), self.beta_1, self.beta_2, self.epsilon,
+                         self.clipvalue or 0.0, int(constrain), max_weight if constrain else 0.0,
+                         L.stream_ptr(stream)), what)
+            if st.scope == "all" and st.fold_jobs:
+                L.check(L.lib.vtd_fold_layernorm_batch(st.fold_plan.data_ptr(), st.fold_jobs,
+                                                       st.fold_rows, L.BF16,
+                                                       L.stream_ptr(stream)),
+                        "vtd_fold_layernorm_batch")
         self.iterations += 1
         model._head_dirty = True
+        if st.scope == "all":
+            model._enc_dirty = True
 
 
 class _State:
-    """m, v, the gradient buffers and the uploaded table for one model's head."""
+    """m, v, the gradient buffers and the uploaded table for one model: its head (scope "head")
+    or every weight (scope "all", with the fp32 staging operands and the job table of the
+    LayerNorm fold where the model was packed with it)."""
 
-    def __init__(self, model):
+    def __init__(self, model, scope="head"):
         if model.dtype not in (L.BF16X3, L.BF16):
-            raise ValueError("Adam: the head trains in the 'bf16x3' and 'bfloat16' modes only "
+            raise ValueError("Adam: the model trains in the 'bf16x3' and 'bfloat16' modes only "
                              "(not float32 / float8)")
         self.model = weakref.ref(model)
         self.master_of = model._master
+        self.scope = scope
+        self.fold_jobs = 0
+        if scope == "all":
+            self._build_all(model)
+            return
         w = model._head_master()
         with torch.cuda.device(model.device):
             self.m = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
@@ -126,6 +167,75 @@ class _State:
             self.plan = torch.empty(need.value, dtype=torch.uint8, device=model.device)
             L.check(L.lib.vtd_adam_plan_upload(table, len(w), model.dtype, self.plan.data_ptr(),
                                                need.value, L.stream_ptr()), "vtd_adam_plan_upload")
+        self.n, self.tiles = len(w), int(tiles.value)
+
+    def _build_all(self, model):
+        """The vtd_train_step table over every tensor of weight_names(): the device masters
+        `gradients` reads (`_encoder_master()` + `_head_master()`) and, per tensor, the
+        destination `Model._pack` recorded -- the packed operand in the mode's format with
+        vtd_pack_dense's / vtd_pack_vector's grouping, or for a layer whose LayerNorm is folded
+        a persistent fp32 staging operand [N_p][K_p] (allocated here, not at model
+        construction) that the fold job reads after the step."""
+        w = OrderedDict(model._encoder_master())
+        w.update(model._head_master())
+        assert list(w) == model.weight_names()
+        with torch.cuda.device(model.device):
+            self.m = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
+            self.v = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
+            self.grads = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
+            self.staging = [torch.zeros(j["shape"], dtype=torch.float32, device=model.device)
+                            for j in model._fold_jobs]
+            table = (L.VtdTrainTensor * len(w))()
+            for d, (n, t) in zip(table, w.items()):
+                where = model._train_packed[n]
+                d.w, d.m, d.v, d.g = (t.data_ptr(), self.m[n].data_ptr(), self.v[n].data_ptr(),
+                                      self.grads[n].data_ptr())
+                folded = where["fold"] is not None
+                packed = self.staging[where["fold"]] if folded else where["t"]
+                d.packed = packed.data_ptr()
+                d.packed_dtype = L.TRAIN_PACK_F32 if folded else L.TRAIN_PACK_MODE
+                d.row_offset = where["off"]
+                d.constrain, d.rule = 1, L.TRAIN_RULE_DENSE
+                if n.endswith("/embeddings"):
+                    # the position embedding (tokens, 1): Keras's sparse Adam path, and the
+                    # reference leaves it without the ClipWeight constraint
+                    d.kind, d.K, d.N, d.ld = L.ADAM_VECTOR, 1, t.numel(), 0
+                    d.constrain, d.rule = 0, L.TRAIN_RULE_SPARSE
+                elif n.endswith("/kernel"):
+                    # EinsumDense kernels: (D, H, dk) is [D][H dk], grouped along N;
+                    # attention_output (H, dk, D) is [H dk][D], grouped along K
+                    w2 = (t.reshape(-1, t.shape[-1]) if t.dim() == 3 and where["kg"] is not None
+                          else t.reshape(t.shape[0], -1))
+                    d.kind, d.K, d.N, d.ld = L.ADAM_MATRIX, w2.shape[0], w2.shape[1], packed.shape[1]
+                    kp = d.ld // 3 if model.dtype == L.BF16X3 and not folded else d.ld
+                    d.k_group, d.k_group_p = where["kg"] or d.K, where["kgp"] or kp
+                else:
+                    d.kind, d.K, d.N, d.ld = L.ADAM_VECTOR, 1, t.numel(), 0
+                d.n_group, d.n_group_p = where["ng"] or d.N, where["ngp"] or d.N
+            need, tiles = ctypes.c_size_t(), ctypes.c_int()
+            L.check(L.lib.vtd_train_plan_bytes(table, len(w), model.dtype, ctypes.byref(need),
+                                               ctypes.byref(tiles)), "vtd_train_plan_bytes")
+            self.plan = torch.empty(need.value, dtype=torch.uint8, device=model.device)
+            L.check(L.lib.vtd_train_plan_upload(table, len(w), model.dtype, self.plan.data_ptr(),
+                                                need.value, L.stream_ptr()),
+                    "vtd_train_plan_upload")
+            if model._fold_jobs:
+                jobs = (L.VtdFoldJob * len(model._fold_jobs))()
+                for j, job, w32 in zip(jobs, model._fold_jobs, self.staging):
+                    n_p, k_p = job["shape"]
+                    j.w32, j.gamma, j.beta = (w32.data_ptr(), job["gamma"].data_ptr(),
+                                              job["beta"].data_ptr())
+                    j.bias_in, j.w_out = job["bias_in"].data_ptr(), job["wo"].data_ptr()
+                    j.bias_out, j.colsum = job["bo"].data_ptr(), job["cs"].data_ptr()
+                    j.N, j.K, j.ldw, j.ldo = n_p, k_p, k_p, k_p
+                self.fold_plan = torch.empty(ctypes.sizeof(jobs), dtype=torch.uint8,
+                                             device=model.device)
+                rows = ctypes.c_int()
+                L.check(L.lib.vtd_fold_plan_upload(jobs, len(jobs), L.BF16,
+                                                   self.fold_plan.data_ptr(), ctypes.sizeof(jobs),
+                                                   ctypes.byref(rows), L.stream_ptr()),
+                        "vtd_fold_plan_upload")
+                self.fold_jobs, self.fold_rows = len(jobs), int(rows.value)
         self.n, self.tiles = len(w), int(tiles.value)
 
 
