@@ -812,55 +812,27 @@ int vtd_stem_backward(const vtd_stem_dims* dims, const vtd_stem_params* params,
                       const float* images_dev, const float* dx0_dev, float* x0_dev,
                       const vtd_stem_grads* grads, void* ws, size_t ws_bytes, void* stream);
 
-/* ---- optimizer step: keras.optimizers.Adam + the ClipWeight constraint + the operand re-pack
- * One tensor of the table: w, m, v (updated in place) and g (read only), fp32 device arrays
- * in the Keras layout with 16-B aligned bases.  VTD_ADAM_MATRIX: a kernel [K][N] row-major;
- * `packed` (nullable: update the master only) is the forward's operand W^T [N_p][ld] of it --
- * VTD_BF16: bf16 rows, K_p = ld; VTD_BF16X3: the split-bf16 B operand [hi | hi | lo] with
- * piece width K_p = ld / 3 -- 16-B aligned, K_p >= K, K_p % 8 == 0.  VTD_ADAM_VECTOR: a bias
- * [N] (K and ld unused); `packed` (nullable) is the fp32 padded vector vtd_pack_vector writes.
- * Padding rule: for rows n < N of a matrix's operand the step writes columns [0, K_p) of each
- * piece, zeros in [K, K_p), and for a vector elements [0, N); rows >= N, elements >= N and
- * everything outside the buffers stay untouched. */
+/* ---- optimizer step: keras.optimizers.Adam + the ClipWeight constraint + the operand re-pack,
+ * ONE kernel over a table of tensors.  The table entry is vtd_train_tensor (below);
+ * vtd_adam_tensor is the ungrouped, always-constrained, dense-rule form of vtd_train_tensor:
+ *   k_group = K, k_group_p = K_p, n_group = n_group_p = N, row_offset = 0, constrain = 1,
+ *   rule = VTD_TRAIN_RULE_DENSE, packed_dtype = packed ? VTD_TRAIN_PACK_MODE : VTD_TRAIN_PACK_NONE
+ * and the vtd_adam_* entries are adapters that convert their table and run the vtd_train_* code:
+ * the same checks, plan layout, kernel and bits.
+ * One tensor: w, m, v (updated in place) and g (read only), fp32 device arrays in the Keras
+ * layout with 16-B aligned bases.  VTD_ADAM_MATRIX: a kernel [K][N] row-major; `packed`
+ * (nullable: update the master only) is the forward's operand W^T [N_p][ld] of it -- VTD_BF16:
+ * bf16 rows, K_p = ld; VTD_BF16X3: the split-bf16 B operand [hi | hi | lo] with piece width
+ * K_p = ld / 3 -- 16-B aligned, K_p >= K, K_p % 8 == 0.  VTD_ADAM_VECTOR: a bias [N] (K and ld
+ * unused); `packed` (nullable) is the fp32 padded vector vtd_pack_vector writes, 4-B aligned. */
 enum { VTD_ADAM_MATRIX = 0, VTD_ADAM_VECTOR = 1 };
 typedef struct vtd_adam_tensor {
   float* w; float* m; float* v; const float* g;
   void* packed;
   int kind, K, N, ld;
 } vtd_adam_tensor;
-/* The plan: the table in its device form plus a tile -> tensor map, built and uploaded ONCE
- * per optimizer state into caller-owned device memory (plan_dev, 16-B aligned, plan_bytes >=
- * what vtd_adam_plan_bytes returns; *tiles is the grid vtd_adam_step launches).  `tensors` is
- * a host array.  vtd_adam_plan_upload copies on `stream` and waits for the copy (the only
- * synchronising entry of the three).  `dtype`: the packed operands' mode.
- * VTD_ERR_INVALID_ARG before any device call: null pointers (the table, w / m / v / g, the
- * outputs, plan_dev), non-positive sizes, misaligned bases, and for a packed destination a
- * dtype other than VTD_BF16 / VTD_BF16X3, ld % 3 != 0 in VTD_BF16X3, ld too small (K_p < K),
- * K_p % 8 != 0; plan_bytes too small. */
-int vtd_adam_plan_bytes(const vtd_adam_tensor* tensors, int n_tensors, int dtype, size_t* bytes,
-                        int* tiles);
-int vtd_adam_plan_upload(const vtd_adam_tensor* tensors, int n_tensors, int dtype,
-                         void* plan_dev, size_t plan_bytes, void* stream);
-/* Step t (1, 2, ...) of every tensor of the plan in ONE launch, per element in fp32 and in this
- * order (TF's ApplyAdam functor; every operation rounded once, no FMA contraction):
- *   g  = clipvalue > 0 ? clip(g, -clipvalue, +clipvalue) : g        (a NaN passes through)
- *   m += (g - m) * (1 - beta1);   v += (g * g - v) * (1 - beta2)
- *   w -= (m * alpha) / (sqrt(v) + epsilon)
- *   w  = constrain ? clip(isnan(w) ? 1.0 : w, -max_weight, +max_weight) : w     (ClipWeight)
- * alpha = learning_rate sqrt(1 - beta2^t) / (1 - beta1^t) is formed on the host in double (from
- * the fp32 betas) and rounded to fp32 once; 1 - beta in fp32.  The packed destinations receive
- * the new w through the conversions of vtd_pack_dense / vtd_split_bf16x3 (role 1): the same
- * bytes as those calls on the updated master.  n_tensors and tiles: as given to / returned by
- * the plan entries.  Asynchronous on `stream`; no copy, no allocation, no host synchronisation;
- * no atomics, bit-identical from run to run.  VTD_ERR_INVALID_ARG before any device call: a
- * null plan, non-positive n_tensors / tiles, t < 1, constrain with max_weight <= 0. */
-int vtd_adam_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
-                  double learning_rate, float beta1, float beta2, float epsilon, float clipvalue,
-                  int constrain, float max_weight, void* stream);
-
-/* ---- whole-model training step: the table entry that can express every operand Model._pack
- * builds with vtd_pack_dense / vtd_pack_vector, a per-tensor destination format, constraint flag
- * and update rule.  w, m, v, g as in vtd_adam_tensor.
+/* The full table entry: what expresses every operand Model._pack builds with vtd_pack_dense /
+ * vtd_pack_vector, a per-tensor destination format, constraint flag and update rule.
  *   VTD_ADAM_MATRIX [K][N]: element (k, n) goes to packed row
  *     row_offset + (n / n_group) * n_group_p + n % n_group, packed column
  *     k' = (k / k_group) * k_group_p + k % k_group (vtd_pack_dense's map; K % k_group == 0,
@@ -875,14 +847,16 @@ int vtd_adam_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
  *     vtd_fold_layernorm reads).
  *   constrain: 0 exempts the tensor from ClipWeight whatever the step asks for (the reference
  *     leaves the position embedding unconstrained).
- *   rule: VTD_TRAIN_RULE_DENSE is vtd_adam_step's; VTD_TRAIN_RULE_SPARSE is the order of Keras's
- *     sparse Adam path, which an Embedding's gradient takes (every index once: a dense update):
+ *   rule: VTD_TRAIN_RULE_DENSE is TF's ApplyAdam functor order (at the step entries below);
+ *     VTD_TRAIN_RULE_SPARSE is the order of Keras's sparse Adam path, which an Embedding's
+ *     gradient takes (every index once: a dense update):
  *       m = m * beta1 + g * (1 - beta1);   v = v * beta2 + (g * g) * (1 - beta2)
  *       w = w - (alpha * m) / (sqrt(v) + epsilon)            same alpha, g clipped first
  * Padding rule: for every real n the step writes the whole piece(s) [0, K_p) of its packed row,
- * zeros at every k' that is no image of a real k; packed rows that are no image of a real n
- * (the pad rows inside a group, the rows of other tensors sharing the buffer) and everything
- * outside the buffers stay untouched. */
+ * zeros at every k' that is no image of a real k (ungrouped: zeros in [K, K_p)); packed rows that
+ * are no image of a real n (the pad rows inside a group, rows >= N, the rows of other tensors
+ * sharing the buffer), vector elements that are no image of an n < N and everything outside the
+ * buffers stay untouched. */
 enum { VTD_TRAIN_PACK_NONE = 0, VTD_TRAIN_PACK_MODE = 1, VTD_TRAIN_PACK_F32 = 2 };
 enum { VTD_TRAIN_RULE_DENSE = 0, VTD_TRAIN_RULE_SPARSE = 1 };
 typedef struct vtd_train_tensor {
@@ -892,21 +866,47 @@ typedef struct vtd_train_tensor {
   int k_group, k_group_p, n_group, n_group_p, row_offset;
   int packed_dtype, constrain, rule;
 } vtd_train_tensor;
-/* The plan entries and the step: as vtd_adam_plan_bytes / vtd_adam_plan_upload / vtd_adam_step,
- * over vtd_train_tensor (one launch for the whole table, every element owned by one thread, no
- * atomics, no allocation, no host read in the step).  VTD_ERR_INVALID_ARG before any device call:
- * everything the vtd_adam_* entries reject, and a bad packed_dtype / rule, packed_dtype NONE
- * with a destination or a destination without one, VTD_TRAIN_PACK_MODE with a dtype other than
- * VTD_BF16 / VTD_BF16X3, non-positive groups, k_group_p < k_group, n_group_p < n_group,
- * K % k_group != 0, N % n_group != 0, a negative row_offset, ld too small for the last real k',
- * K_p % 8 != 0. */
+/* The plan: the table in its device form plus a tile -> tensor map, built and uploaded ONCE
+ * per optimizer state into caller-owned device memory (plan_dev, 16-B aligned, plan_bytes >=
+ * what the plan_bytes entry returns; *tiles is the grid the step launches).  `tensors` is a host
+ * array.  The plan_upload entry copies on `stream` and waits for the copy (the only
+ * synchronising entry of the three).  `dtype`: the packed operands' mode.
+ * VTD_ERR_INVALID_ARG before any device call: null pointers (the table, w / m / v / g, the
+ * outputs, plan_dev), non-positive sizes, misaligned bases, a bad kind / packed_dtype / rule,
+ * packed_dtype NONE with a destination or a destination without one, VTD_TRAIN_PACK_MODE (any
+ * vtd_adam_tensor destination) with a dtype other than VTD_BF16 / VTD_BF16X3, non-positive
+ * groups, k_group_p < k_group, n_group_p < n_group, K % k_group != 0, N % n_group != 0, a negative
+ * row_offset, ld % 3 != 0 in VTD_BF16X3, ld too small (K_p < the last real k' + 1; ungrouped:
+ * K_p < K), K_p % 8 != 0; plan_bytes too small. */
 int vtd_train_plan_bytes(const vtd_train_tensor* tensors, int n_tensors, int dtype, size_t* bytes,
                          int* tiles);
 int vtd_train_plan_upload(const vtd_train_tensor* tensors, int n_tensors, int dtype,
                           void* plan_dev, size_t plan_bytes, void* stream);
+int vtd_adam_plan_bytes(const vtd_adam_tensor* tensors, int n_tensors, int dtype, size_t* bytes,
+                        int* tiles);
+int vtd_adam_plan_upload(const vtd_adam_tensor* tensors, int n_tensors, int dtype,
+                         void* plan_dev, size_t plan_bytes, void* stream);
+/* Step t (1, 2, ...) of every tensor of the plan in ONE launch, per element in fp32 and in this
+ * order (VTD_TRAIN_RULE_DENSE; every operation rounded once, no FMA contraction):
+ *   g  = clipvalue > 0 ? clip(g, -clipvalue, +clipvalue) : g        (a NaN passes through)
+ *   m += (g - m) * (1 - beta1);   v += (g * g - v) * (1 - beta2)
+ *   w -= (m * alpha) / (sqrt(v) + epsilon)
+ *   w  = constrain ? clip(isnan(w) ? 1.0 : w, -max_weight, +max_weight) : w     (ClipWeight;
+ *        `constrain` and the tensor's own flag)
+ * alpha = learning_rate sqrt(1 - beta2^t) / (1 - beta1^t) is formed on the host in double (from
+ * the fp32 betas) and rounded to fp32 once; 1 - beta in fp32.  The packed destinations receive
+ * the new w through the conversions of vtd_pack_dense / vtd_split_bf16x3 (role 1): the same
+ * bytes as those calls on the updated master.  n_tensors and tiles: as given to / returned by
+ * the plan entries.  Asynchronous on `stream`; no copy, no allocation, no host synchronisation;
+ * every element owned by one thread, no atomics, bit-identical from run to run.
+ * VTD_ERR_INVALID_ARG before any device call: a null plan, non-positive n_tensors / tiles,
+ * t < 1, constrain with max_weight <= 0. */
 int vtd_train_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
                    double learning_rate, float beta1, float beta2, float epsilon, float clipvalue,
                    int constrain, float max_weight, void* stream);
+int vtd_adam_step(const void* plan_dev, int n_tensors, int tiles, int64_t t,
+                  double learning_rate, float beta1, float beta2, float epsilon, float clipvalue,
+                  int constrain, float max_weight, void* stream);
 
 /* The LayerNorm fold of several layers in ONE launch: job j is vtd_fold_layernorm(w32, N, K,
  * ldw, gamma, beta, bias_in, w_out, ldo, dtype, bias_out, colsum) with the same per-row

@@ -76,6 +76,21 @@ def test_sparse_clip_and_constraint():
     np.testing.assert_allclose(v, vd, rtol=1e-12)
 
 
+def test_sparse_nan_goes_to_one_under_the_constraint():
+    """ClipWeight maps a NaN weight to 1.0 before the clip (the kernel's `w != w ? 1 : w`), in
+    the sparse order exactly as in step32; m and v stay NaN.  An inf gradient is clipped."""
+    w0 = np.array([0.3, -0.7, 9.9995, 2.0], np.float32)
+    z = np.zeros_like(w0)
+    g = np.array([np.nan, 0.5, -np.inf, np.inf], np.float32)
+    a = T.sparse32(w0, z, z, g, 1, LR, clipvalue=10.0, max_weight=10.0, constrain=True)
+    b = A.step32(w0, z, z, g, 1, LR, clipvalue=10.0, max_weight=10.0, constrain=True)
+    for w, m, v in (a, b):
+        assert w[0] == 1.0 and np.isnan(m[0]) and np.isnan(v[0])
+        assert w[2] == np.float32(10.0) and np.isfinite(w[1:]).all() and w[3] < w0[3]
+    free = T.sparse32(w0, z, z, g, 1, LR, clipvalue=10.0, constrain=False)
+    assert np.isnan(free[0][0]) and free[0][2] > 10.0
+
+
 # ------------------------------------------------------------------ the grouped pack, the fold
 def test_grouped_pack_restated():
     # no groups: adam_oracle.pack_ref
@@ -214,6 +229,51 @@ def test_train_plan_argument_checks_need_no_device(L):
         assert word in L.lib.vtd_last_error(), (what, L.lib.vtd_last_error())
         with pytest.raises(ValueError):
             L.check(L.lib.vtd_train_plan_upload(*args), "vtd_train_plan_upload")
+
+
+@pytest.mark.parametrize("mode", ["bf16", "bf16x3", None])
+def test_adam_table_plans_as_its_train_form(L, mode):
+    """vtd_adam_tensor is the ungrouped, always-constrained, dense-rule form of vtd_train_tensor:
+    for every tensor of tests/test_gpu_adam.py SPECS, alone and all in one table, in each dtype
+    that file uses (None: VTD_F32 without destinations), vtd_adam_plan_bytes and
+    vtd_train_plan_bytes over the train form written out here give the same tiles and bytes.
+    The pointers are never dereferenced."""
+    from tests.test_gpu_adam import SPECS, up64
+    dtype = {"bf16": L.BF16, "bf16x3": L.BF16X3, None: L.F32}[mode]
+    pieces = {"bf16": 1, "bf16x3": 3, None: 0}[mode]
+    adam, train = [], []
+    for i, (shape, kp) in enumerate(SPECS):
+        at = 4096 * (i + 1)
+        ptrs = dict(w=at, m=at + 16, v=at + 32, g=at + 48, packed=at + 64 if mode else None)
+        if len(shape) == 2:
+            K, N = shape
+            k_p = kp or up64(K)
+            dims = dict(kind=L.ADAM_MATRIX, K=K, N=N, ld=pieces * k_p)
+        else:
+            K, N, k_p = 0, shape[0], 0
+            dims = dict(kind=L.ADAM_VECTOR, K=0, N=N, ld=0)
+        adam.append(L.VtdAdamTensor(**ptrs, **dims))
+        train.append(L.VtdTrainTensor(
+            **ptrs, **dims, k_group=K, k_group_p=k_p if mode else 0, n_group=N, n_group_p=N,
+            row_offset=0, packed_dtype=L.TRAIN_PACK_MODE if mode else L.TRAIN_PACK_NONE,
+            constrain=1, rule=L.TRAIN_RULE_DENSE))
+
+    def plans(which):
+        out = []
+        for entry, kind, table in ((L.lib.vtd_adam_plan_bytes, L.VtdAdamTensor, adam),
+                                   (L.lib.vtd_train_plan_bytes, L.VtdTrainTensor, train)):
+            nbytes, tiles = ctypes.c_size_t(), ctypes.c_int()
+            arr = (kind * len(which))(*[table[i] for i in which])
+            assert entry(arr, len(which), dtype, ctypes.byref(nbytes), ctypes.byref(tiles)) == 0, \
+                L.lib.vtd_last_error()
+            out.append((tiles.value, nbytes.value))
+        return out
+
+    for which in [[i] for i in range(len(SPECS))] + [list(range(len(SPECS)))]:
+        a, t = plans(which)
+        assert a == t and a[0] > 0 and a[1] > 0, (which, a, t)
+    # 130 x 6 with K_p = 256: four K tiles with a destination (one is pure padding), else three
+    assert plans([2])[0][0] == (4 if mode else 3)
 
 
 def test_train_step_argument_checks_need_no_device(L):

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Timing of the head's optimizer step on the C2 head (presets.VIT_B16_224), bf16 and bf16x3.
 
-  fused    one vtd_adam_step launch: Adam + ClipWeight + the re-pack of the packed operands
-  unfused  vtd_adam_step without packed destinations, then per tensor vtd_pack_dense (in
-           bf16x3: to an fp32 staging matrix, then vtd_split_bf16x3) / vtd_pack_vector
+  fused    optimizers.Adam.apply in scope "head": one vtd_train_step launch over the head's
+           table -- Adam + ClipWeight + the re-pack of the packed operands
+  unfused  vtd_adam_step over a master-only table (the same kernel through the vtd_adam_*
+           entries, no destinations), then per tensor vtd_pack_dense (in bf16x3: to an fp32
+           staging matrix, then vtd_split_bf16x3) / vtd_pack_vector
 
 A and B alternate in rounds inside one process (device events around `--iters` calls each);
 the medians and the spread over the rounds are reported, with the achieved TB/s against the
@@ -62,10 +64,11 @@ def unfused_route(model, opt):
     L.check(L.lib.vtd_adam_plan_upload(table, len(w), model.dtype, plan.data_ptr(), need.value,
                                        L.stream_ptr()), "plan_upload")
     x3 = model.dtype == L.BF16X3
+    packed = {n: model._train_packed[n]["t"] for n in w}
     staging = {}
     for n, t in w.items():
         if t.dim() == 2 and x3:
-            rows_p, ld = model._head_packed[n].shape
+            rows_p, ld = packed[n].shape
             staging[n] = torch.zeros((rows_p, ld // 3), dtype=torch.float32, device=model.device)
 
     def run():
@@ -73,7 +76,7 @@ def unfused_route(model, opt):
         L.check(L.lib.vtd_adam_step(plan.data_ptr(), len(w), tiles.value, 1, 1e-3, 0.9, 0.999,
                                     1e-7, 10.0, 1, 10.0, s), "adam_step")
         for n, t in w.items():
-            p = model._head_packed[n]
+            p = packed[n]
             if t.dim() == 1:
                 L.check(L.lib.vtd_pack_vector(t.data_ptr(), t.numel(), t.numel(), t.numel(),
                                               p.data_ptr(), 0, s), "pack_vector")

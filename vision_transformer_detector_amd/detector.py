@@ -268,15 +268,16 @@ class Model:
         tdt = _TORCH_DTYPE[dt]
         dev = self.device
         keep, staging = [], []
-        head = {}        # Keras name -> packed tensor of the head (vtd_adam_step re-packs them)
         # Keras name -> where the forward's copy of that tensor lives (vtd_train_step re-packs
         # it): the packed tensor `t` and vtd_pack_dense's / vtd_pack_vector's grouping, or
         # `fold`: the index in `folds` of the LayerNorm fold job whose fp32 staging operand it
-        # belongs to.  Not filled for the MX-fp8 layers (no training in that mode).
+        # belongs to.  Not filled for the MX-fp8 layers (no training in that mode).  `rec` returns
+        # the packed tensor's device pointer, for the forward's weight struct.
         train, folds = {}, []
 
         def rec(name, t=None, fold=None, kg=None, kgp=None, ng=None, ngp=None, off=0):
             train[name] = dict(t=t, fold=fold, kg=kg, kgp=kgp, ng=ng, ngp=ngp, off=off)
+            return None if t is None else t.data_ptr()
         stream = L.stream_ptr(torch.cuda.current_stream(dev))
 
         def zeros(*shape, dtype=tdt):
@@ -375,10 +376,9 @@ class Model:
         kw = self.kwargs
         dk, dkp = kw["encoder_key_dim"], dims.key_dim_p
         W = L.VtdWeights()
-        rec("linear_projection/kernel", dense("linear_projection", dims.d_p, dims.patch_dim_p))
-        rec("linear_projection/bias", vector("linear_projection/bias", dims.d_p))
-        W.w_patch = train["linear_projection/kernel"]["t"].data_ptr()
-        W.b_patch = train["linear_projection/bias"]["t"].data_ptr()
+        W.w_patch = rec("linear_projection/kernel",
+                        dense("linear_projection", dims.d_p, dims.patch_dim_p))
+        W.b_patch = rec("linear_projection/bias", vector("linear_projection/bias", dims.d_p))
         pos = src("position_encoding/position_embedding/embeddings").reshape(-1)
         keep.append(pos)
         rec("position_encoding/position_embedding/embeddings", pos)
@@ -421,8 +421,8 @@ class Model:
             # attention_output kernel (H, dk, D) -> (H*dk, D); rows padded per head
             Ly.w_out, Ly.s_out = enc(f"{mha}/attention_output", dims.d_p, dims.inner_p, kg=dk,
                                      kgp=dkp)
-            rec(f"{mha}/attention_output/bias", vector(f"{mha}/attention_output/bias", dims.d_p))
-            Ly.b_out = train[f"{mha}/attention_output/bias"]["t"].data_ptr()
+            Ly.b_out = rec(f"{mha}/attention_output/bias",
+                           vector(f"{mha}/attention_output/bias", dims.d_p))
             k_p = dims.d_p
             for j in range(kw["encoder_mlp_quantities"]):
                 n_p = dims.mlp_units_p[j]
@@ -437,27 +437,19 @@ class Model:
                     Ly.b_mlp[j] = bm.data_ptr()
                 k_p = n_p
         W.layers = ctypes.cast(layers, ctypes.POINTER(L.VtdLayerWeights))
-        head["dense/kernel"] = dense("dense", L.KALIGN, dims.d_p)
-        head["dense/bias"] = vector("dense/bias", L.KALIGN)
-        W.w_det, W.b_det = head["dense/kernel"].data_ptr(), head["dense/bias"].data_ptr()
+        W.w_det = rec("dense/kernel", dense("dense", L.KALIGN, dims.d_p))
+        W.b_det = rec("dense/bias", vector("dense/bias", L.KALIGN))
         k_p = dims.tokens_p
         for j in range(dims.n_head):
             n_p = dims.head_units_p[j]
-            head[f"dense_{j + 1}/kernel"] = dense(f"dense_{j + 1}", n_p, k_p)
-            head[f"dense_{j + 1}/bias"] = vector(f"dense_{j + 1}/bias", n_p)
-            W.w_head[j] = head[f"dense_{j + 1}/kernel"].data_ptr()
-            W.b_head[j] = head[f"dense_{j + 1}/bias"].data_ptr()
+            W.w_head[j] = rec(f"dense_{j + 1}/kernel", dense(f"dense_{j + 1}", n_p, k_p))
+            W.b_head[j] = rec(f"dense_{j + 1}/bias", vector(f"dense_{j + 1}/bias", n_p))
             k_p = n_p
-        head["MLP_Head_no_Sigmoid/kernel"] = dense("MLP_Head_no_Sigmoid", L.KALIGN, k_p)
-        head["MLP_Head_no_Sigmoid/bias"] = vector("MLP_Head_no_Sigmoid/bias", L.KALIGN)
-        W.w_final = head["MLP_Head_no_Sigmoid/kernel"].data_ptr()
-        W.b_final = head["MLP_Head_no_Sigmoid/bias"].data_ptr()
+        W.w_final = rec("MLP_Head_no_Sigmoid/kernel", dense("MLP_Head_no_Sigmoid", L.KALIGN, k_p))
+        W.b_final = rec("MLP_Head_no_Sigmoid/bias", vector("MLP_Head_no_Sigmoid/bias", L.KALIGN))
         torch.cuda.current_stream(dev).synchronize()
         del staging      # fp32 staging copies; the packed buffers stay alive in `keep`
         self._packed = keep
-        self._head_packed = head
-        for n, t in head.items():
-            rec(n, t)
         self._train_packed, self._fold_jobs = train, folds
         self._layers_c = layers
         self._weights_c = W
@@ -664,14 +656,18 @@ class Model:
             return OrderedDict((n, live[n].clone()) for n in names)
         return OrderedDict((n, self._master[n].to(self.device).contiguous()) for n in names)
 
+    def _device_master(self, part, names):
+        """fp32 device copies of the weights `names` in the Keras layout, made once per
+        set_weights and held under `part`."""
+        held = self.__dict__.setdefault("_dev_masters", {})
+        if part not in held or held[part][0] is not self._master:
+            held[part] = (self._master, OrderedDict(
+                (n, self._master[n].to(self.device).contiguous()) for n in names))
+        return held[part][1]
+
     def _head_master(self):
-        """fp32 device copies of the head's weights in the Keras layout (vtd_head_params),
-        made once per set_weights."""
-        if getattr(self, "_head_dev_of", None) is not self._master:
-            self._head_dev = OrderedDict(
-                (n, self._master[n].to(self.device).contiguous()) for n in self.head_weight_names())
-            self._head_dev_of = self._master
-        return self._head_dev
+        """The device masters of the head's weights (vtd_head_params)."""
+        return self._device_master("head", self.head_weight_names())
 
     def head_gradients(self, images, y_true, encoded=None):
         """One frozen-encoder training step up to the optimizer update: encoder features ->
@@ -694,15 +690,11 @@ class Model:
         return self._current(list(self.weight_shapes)[:3])
 
     def _encoder_master(self):
-        """fp32 device copies of the stem's and every encoder block's weights in the Keras
-        layout (vtd_stem_params, vtd_block_params), made once per set_weights."""
-        if getattr(self, "_enc_dev_of", None) is not self._master:
-            per = 12 + 2 * self.kwargs["encoder_mlp_quantities"]
-            names = list(self.weight_shapes)[:3 + self.kwargs["encoder_repeat_times"] * per]
-            self._enc_dev = OrderedDict(
-                (n, self._master[n].to(self.device).contiguous()) for n in names)
-            self._enc_dev_of = self._master
-        return self._enc_dev
+        """The device masters of the stem's and every encoder block's weights (vtd_stem_params,
+        vtd_block_params)."""
+        per = 12 + 2 * self.kwargs["encoder_mlp_quantities"]
+        names = list(self.weight_shapes)[:3 + self.kwargs["encoder_repeat_times"] * per]
+        return self._device_master("encoder", names)
 
     def gradients(self, images, y_true):
         """The gradient of the compiled loss with respect to every weight: the training forward
@@ -725,13 +717,7 @@ class Model:
         """The chain gradients and train_on_batch share.  `buffers`: Keras name -> fp32 device
         tensor to write each weight gradient into (the optimizer's persistent ones); None
         allocates fresh tensors.  Returns (out5, grads keyed by `weight_names()`)."""
-        if self.dtype not in (L.BF16X3, L.BF16):
-            raise ValueError(f"{what}: the head backward runs in the 'bf16x3' and "
-                             "'bfloat16' modes only (not float32 / float8)")
-        from . import loss as _loss
-        if self.loss is None or _loss.fused_loss_params(self.loss) is None:
-            raise ValueError(f"{what}: compile(loss=my_custom_loss or a functools.partial "
-                             "of it with keyword arguments) first")
+        self._require(what)
         from . import encoder as _enc
         from . import stem as _stem
         x = self._as_images(images)
@@ -779,24 +765,72 @@ class Model:
             found = g + found + list(head.values())
         return out5, OrderedDict(zip(self.weight_shapes, found))
 
-    # ---- whole-model training (vtd_train_step, vtd_fold_layernorm_batch; optimizers.py)
-    def _training_optimizer(self, what):
-        if self.dtype not in (L.BF16X3, L.BF16):
-            raise ValueError(f"{what}: the model trains in the 'bf16x3' and 'bfloat16' modes "
-                             "only (not float32 / float8)")
-        if self.kwargs.get("dropout"):
+    # ---- what the gradient and training calls share
+    def _require(self, what, mode=True, loss=True, optimizer=False, whole_model=False):
+        """The preconditions of the gradient and training calls, for the caller `what`, in this
+        order: the mode (`mode`), for whole-model training (`whole_model`) a model without
+        dropout, a compiled fused loss (`loss`), a resolvable compiled optimizer (`optimizer`).
+        Returns (the fused loss parameters, the optimizer), None where not asked for."""
+        if mode and self.dtype not in (L.BF16X3, L.BF16):
+            does = "model trains" if whole_model else "head backward runs"
+            raise ValueError(f"{what}: the {does} in the 'bf16x3' and 'bfloat16' modes only "
+                             "(not float32 / float8)")
+        if whole_model and self.kwargs.get("dropout"):
             raise ValueError(f"{what}: the training graph here is the dropout=None graph; this "
                              f"model was built with dropout={self.kwargs['dropout']!r}")
-        from . import loss as _loss
-        if self.loss is None or _loss.fused_loss_params(self.loss) is None:
-            raise ValueError(f"{what}: compile(loss=my_custom_loss or a functools.partial "
-                             "of it with keyword arguments) first")
-        from . import optimizers as _opt
-        try:
-            return _opt.resolve(self.optimizer)
-        except ValueError as e:
-            raise ValueError(f"{what}: {e}") from None
+        params = resolved = None
+        if loss:
+            from . import loss as _loss
+            params = _loss.fused_loss_params(self.loss) if self.loss is not None else None
+            if params is None:
+                raise ValueError(f"{what}: compile(loss=my_custom_loss or a functools.partial "
+                                 "of it with keyword arguments) first")
+        if optimizer:
+            from . import optimizers as _opt
+            try:
+                resolved = _opt.resolve(self.optimizer)
+            except ValueError as e:
+                raise ValueError(f"{what}: {e}") from None
+        return params, resolved
 
+    def _fit_loop(self, what, optimizer, batches, step, epochs, lr_schedule, callbacks=()):
+        """The epoch loop fit and fit_head share.  `batches()` yields an epoch's (images, labels)
+        pairs and `step(i, images, labels)` trains on the i-th, returning out5.  `set_model(self)`
+        is called once on the callbacks that have it.  Per epoch: `lr_schedule(epoch, lr)` sets
+        the optimizer's rate, the batch losses weighted by batch size add up in a float64[2]
+        device accumulator, ONE host read takes the mean into the History, and every callback
+        that has `on_epoch_end` gets (epoch, {"loss": ...})."""
+        from . import optimizers as _opt
+        from .metrics import _device_f32
+        if int(epochs) < 0:
+            raise ValueError(f"{what}: epochs must be >= 0, got {epochs}")
+        for cb in callbacks:
+            if callable(getattr(cb, "set_model", None)):
+                cb.set_model(self)
+        hist = _opt.History()
+        with torch.cuda.device(self.device):
+            running = torch.zeros(2, dtype=torch.float64, device=self.device)
+            for epoch in range(int(epochs)):
+                if lr_schedule is not None:
+                    optimizer.learning_rate = float(lr_schedule(epoch, optimizer.learning_rate))
+                running.zero_()
+                for i, (images, labels) in enumerate(batches()):
+                    n = len(labels)
+                    if n == 0:
+                        continue
+                    out5 = step(i, images, _device_f32(labels, self.device))
+                    running[0] += out5[0].double() * n
+                    running[1] += n
+                total, count = running.cpu().tolist()       # the epoch's one host read
+                loss = total / count if count else float("nan")
+                hist.history["loss"].append(loss)
+                hist.epoch.append(epoch)
+                for cb in callbacks:
+                    if callable(getattr(cb, "on_epoch_end", None)):
+                        cb.on_epoch_end(epoch, {"loss": loss})
+        return hist
+
+    # ---- whole-model training (vtd_train_step, vtd_fold_layernorm_batch; optimizers.py)
     def train_on_batch(self, images, y_true):
         """keras.Model.train_on_batch over every weight: gradients' chain with each weight
         gradient written into the compiled optimizer's persistent buffers, then ONE
@@ -810,7 +844,7 @@ class Model:
         get_weight_dict / save_weights read them back on demand.  Needs
         compile(optimizer=optimizers.Adam(...) or 'adam', loss=my_custom_loss or a
         functools.partial of it), dtype 'bf16x3' or 'bfloat16' and a model without dropout."""
-        optimizer = self._training_optimizer("train_on_batch")
+        _, optimizer = self._require("train_on_batch", optimizer=True, whole_model=True)
         out5, _ = self._grad_chain("train_on_batch", images, y_true,
                                    optimizer.gradient_buffers(self, scope="all"))
         optimizer.apply(self, scope="all")
@@ -828,58 +862,26 @@ class Model:
         one float per epoch: the mean of the batch losses weighted by batch size, accumulated
         on the device and read once per epoch."""
         del verbose
-        from . import optimizers as _opt
-        from .metrics import _device_f32
-        optimizer = self._training_optimizer("fit")
-        if int(epochs) < 0:
-            raise ValueError(f"fit: epochs must be >= 0, got {epochs}")
-        callbacks = list(callbacks or [])
-        for cb in callbacks:
-            if callable(getattr(cb, "set_model", None)):
-                cb.set_model(self)
-        hist = _opt.History()
-        with torch.cuda.device(self.device):
-            running = torch.zeros(2, dtype=torch.float64, device=self.device)
-            for epoch in range(int(epochs)):
-                if lr_schedule is not None:
-                    optimizer.learning_rate = float(lr_schedule(epoch, optimizer.learning_rate))
-                running.zero_()
-                for images, labels in self._evaluate_batches(x, y, batch_size):
-                    n = len(labels)
-                    if n == 0:
-                        continue
-                    out5 = self.train_on_batch(images, _device_f32(labels, self.device))
-                    running[0] += out5[0].double() * n
-                    running[1] += n
-                total, count = running.cpu().tolist()       # the epoch's one host read
-                loss = total / count if count else float("nan")
-                hist.history["loss"].append(loss)
-                hist.epoch.append(epoch)
-                for cb in callbacks:
-                    if callable(getattr(cb, "on_epoch_end", None)):
-                        cb.on_epoch_end(epoch, {"loss": loss})
-        return hist
+        _, optimizer = self._require("fit", optimizer=True, whole_model=True)
+        return self._fit_loop("fit", optimizer, lambda: self._evaluate_batches(x, y, batch_size),
+                              lambda i, images, labels: self.train_on_batch(images, labels),
+                              epochs, lr_schedule, list(callbacks or []))
 
-    # ---- head training (vtd_adam_step; optimizers.py)
+    # ---- head training (the same vtd_train_step over the head's tensors; optimizers.py)
     def train_head_on_batch(self, images, y_true, encoded=None):
         """keras.Model.train_on_batch for the detection head on a frozen encoder: head_gradients'
         pass with the weight gradients written into the compiled optimizer's persistent buffers,
-        then ONE vtd_adam_step launch -- Adam, the ClipWeight constraint (`max_weight` /
-        `clip_weight` of the model's kwargs) and the re-pack of the forward's head operands.
+        then ONE vtd_train_step launch over the head's tensors -- Adam, the ClipWeight constraint
+        (`max_weight` / `clip_weight` of the model's kwargs) and the re-pack of the forward's head
+        operands.
         Returns out5 as head_gradients does, taken before the update, as Keras reports the
         loss; nothing is read back to the host.  Afterwards the device masters
         (`_head_master()`) are the truth for the head; get_weights / get_weight_dict /
         save_weights read them back on demand.  Needs compile(optimizer=optimizers.Adam(...) or
         'adam', loss=my_custom_loss or a functools.partial of it) and dtype 'bf16x3' or
         'bfloat16'."""
-        if self.dtype not in (L.BF16X3, L.BF16):
-            raise ValueError("train_head_on_batch: the head backward runs in the 'bf16x3' and "
-                             "'bfloat16' modes only (not float32 / float8)")
-        from . import optimizers as _opt
-        try:
-            optimizer = _opt.resolve(self.optimizer)
-        except ValueError as e:
-            raise ValueError(f"train_head_on_batch: {e}") from None
+        # the compiled loss is _head_pass's check: a missing optimizer is reported first
+        _, optimizer = self._require("train_head_on_batch", loss=False, optimizer=True)
         out5, _ = self._head_pass("train_head_on_batch", images, y_true, encoded,
                                   weight_grads=optimizer.gradient_buffers(self, scope="head"))
         optimizer.apply(self, scope="head")
@@ -899,50 +901,24 @@ class Model:
         Returns an object whose .history["loss"] holds one float per epoch: the mean of the
         batch losses weighted by batch size (the Keras loss metric), accumulated on the device
         and read once per epoch."""
-        from . import optimizers as _opt
-        from .metrics import _device_f32
-        try:
-            optimizer = _opt.resolve(self.optimizer)
-        except ValueError as e:
-            raise ValueError(f"fit_head: {e}") from None
-        if int(epochs) < 0:
-            raise ValueError(f"fit_head: epochs must be >= 0, got {epochs}")
+        # the mode and the loss are train_head_on_batch's checks, per batch
+        _, optimizer = self._require("fit_head", mode=False, loss=False, optimizer=True)
         if encoded is not None:
             if y is None:
                 raise ValueError("fit_head: encoded= needs the labels in y")
-            batches = list(self._evaluate_batches(encoded, y, batch_size))
-            features = [b[0] for b in batches]
+            fixed = list(self._evaluate_batches(encoded, y, batch_size))
+            features = [b[0] for b in fixed]
+            batches = lambda: fixed                                        # noqa: E731
         else:
-            batches = None
             features = {}
-        hist = _opt.History()
-        with torch.cuda.device(self.device):
-            running = torch.zeros(2, dtype=torch.float64, device=self.device)
-            for epoch in range(int(epochs)):
-                if lr_schedule is not None:
-                    optimizer.learning_rate = float(lr_schedule(epoch, optimizer.learning_rate))
-                running.zero_()
-                source = batches if batches is not None else self._evaluate_batches(x, y, batch_size)
-                for i, (images, labels) in enumerate(source):
-                    n = len(labels)
-                    if n == 0:
-                        continue
-                    if batches is not None:
-                        feats = features[i]
-                    elif cache_features:
-                        if i not in features:
-                            features[i] = self.encode(images)
-                        feats = features[i]
-                    else:
-                        feats = None
-                    out5 = self.train_head_on_batch(images, _device_f32(labels, self.device),
-                                                    encoded=feats)
-                    running[0] += out5[0].double() * n
-                    running[1] += n
-                total, count = running.cpu().tolist()       # the epoch's one host read
-                hist.history["loss"].append(total / count if count else float("nan"))
-                hist.epoch.append(epoch)
-        return hist
+            batches = lambda: self._evaluate_batches(x, y, batch_size)     # noqa: E731
+
+        def step(i, images, labels):
+            if encoded is None and cache_features and i not in features:
+                features[i] = self.encode(images)
+            feats = features[i] if encoded is not None or cache_features else None
+            return self.train_head_on_batch(images, labels, encoded=feats)
+        return self._fit_loop("fit_head", optimizer, batches, step, epochs, lr_schedule)
 
     def _head_pass(self, what, images, y_true, encoded, weight_grads=None):
         """The part head_gradients and train_head_on_batch share: the checks, the encoder
@@ -950,14 +926,8 @@ class Model:
         backward.  `weight_grads`: buffers to write the weight gradients into (the optimizer's
         persistent ones; d loss / d encoded_images is then not computed); None allocates them
         and the encoded_images gradient.  Returns (out5, grads)."""
-        if self.dtype not in (L.BF16X3, L.BF16):
-            raise ValueError(f"{what}: the head backward runs in the 'bf16x3' and "
-                             "'bfloat16' modes only (not float32 / float8)")
         from . import loss as _loss
-        params = _loss.fused_loss_params(self.loss) if self.loss is not None else None
-        if params is None:
-            raise ValueError(f"{what}: compile(loss=my_custom_loss or a functools.partial "
-                             "of it with keyword arguments) first")
+        params, _ = self._require(what)
         dims = self.dims
         with torch.cuda.device(self.device):
             if encoded is None:

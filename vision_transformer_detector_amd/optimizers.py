@@ -2,14 +2,13 @@
 defc2073): keras.optimizers.Adam with `clipvalue`, the ClipWeight constraint (vtd.py:209-236)
 and the step schedule `learning_rate_step_decay` (vtd.py:696-728).
 
-The update itself is one launch of vtd_adam_step per training step (csrc/vtd_optimizer.hip):
-Adam, the constraint and the re-pack of the forward's head operands, over a table of the
-head's tensors that is uploaded once.  There is no host arithmetic on the weights.
-
-The same optimizer trains every weight (Model.train_on_batch / fit, scope "all"): one launch of
-vtd_train_step over a table of all tensors, whose entries carry the grouping, destination format,
-constraint flag and update rule of each, then one launch of vtd_fold_layernorm_batch where the
-model's LayerNorms are folded into the next GEMM's operands.
+The update itself is one launch of vtd_train_step per training step (csrc/vtd_optimizer.hip):
+Adam, the constraint and the re-pack of the forward's operands, over a table of tensors that is
+uploaded once -- the head's (Model.train_head_on_batch / fit_head, scope "head") or every
+weight's (Model.train_on_batch / fit, scope "all").  Its entries carry the grouping, destination
+format, constraint flag and update rule of each tensor; where the table holds layers whose
+LayerNorm is folded into the next GEMM's operands, one launch of vtd_fold_layernorm_batch
+follows.  There is no host arithmetic on the weights.
 """
 from __future__ import annotations
 
@@ -101,10 +100,10 @@ class Adam:
         return st.m, st.v
 
     def apply(self, model, stream=None, scope=None):
-        """One step on `model` from the gradient buffers.  Scope "head": a single vtd_adam_step
-        launch that updates the head's device masters, moments and packed operands.  Scope
-        "all": a single vtd_train_step launch over every weight and, where the model was packed
-        with the LayerNorm fold, one vtd_fold_layernorm_batch launch that refreshes the folded
+        """One step on `model` from the gradient buffers: a single vtd_train_step launch that
+        updates the device masters, moments and packed operands of the scope's tensors (the
+        head's, or every weight's) and, where the scope holds tensors packed with the LayerNorm
+        fold (never the head), one vtd_fold_layernorm_batch launch that refreshes the folded
         operands from the staging the step wrote."""
         st = self._state_for(model, scope)
         constrain = bool(model.kwargs.get("clip_weight", True))
@@ -112,14 +111,13 @@ class Adam:
         if constrain and not max_weight > 0.0:
             raise ValueError(f"Adam: clip_weight needs a positive max_weight, got "
                              f"{model.kwargs.get('max_weight')!r}")
-        step, what = ((L.lib.vtd_train_step, "vtd_train_step") if st.scope == "all" else
-                      (L.lib.vtd_adam_step, "vtd_adam_step"))
         with torch.cuda.device(model.device):
-            L.check(step(st.plan.data_ptr(), st.n, st.tiles, self.iterations + 1,
-                         float(self.learning_rate), self.beta_1, self.beta_2, self.epsilon,
-                         self.clipvalue or 0.0, int(constrain), max_weight if constrain else 0.0,
-                         L.stream_ptr(stream)), what)
-            if st.scope == "all" and st.fold_jobs:
+            L.check(L.lib.vtd_train_step(
+                st.plan.data_ptr(), st.n, st.tiles, self.iterations + 1,
+                float(self.learning_rate), self.beta_1, self.beta_2, self.epsilon,
+                self.clipvalue or 0.0, int(constrain), max_weight if constrain else 0.0,
+                L.stream_ptr(stream)), "vtd_train_step")
+            if st.fold_jobs:
                 L.check(L.lib.vtd_fold_layernorm_batch(st.fold_plan.data_ptr(), st.fold_jobs,
                                                        st.fold_rows, L.BF16,
                                                        L.stream_ptr(stream)),
@@ -131,9 +129,15 @@ class Adam:
 
 
 class _State:
-    """m, v, the gradient buffers and the uploaded table for one model: its head (scope "head")
-    or every weight (scope "all", with the fp32 staging operands and the job table of the
-    LayerNorm fold where the model was packed with it)."""
+    """m, v, the gradient buffers and the uploaded vtd_train_step table for one model: over its
+    head (scope "head": `head_weight_names()`, the device masters of `_head_master()` alone) or
+    over every weight (scope "all": `weight_names()`, `_encoder_master()` + `_head_master()`, the
+    masters `gradients` reads).  Per tensor the destination is what `Model._pack` recorded in
+    `_train_packed` -- the packed operand in the mode's format with vtd_pack_dense's /
+    vtd_pack_vector's grouping, or for a layer whose LayerNorm is folded a persistent fp32
+    staging operand [N_p][K_p] (allocated here, not at model construction) that the fold job
+    reads after the step.  The staging and the fold job table exist only where the scope's
+    tensors include folded ones: never for the head."""
 
     def __init__(self, model, scope="head"):
         if model.dtype not in (L.BF16X3, L.BF16):
@@ -143,58 +147,27 @@ class _State:
         self.master_of = model._master
         self.scope = scope
         self.fold_jobs = 0
-        if scope == "all":
-            self._build_all(model)
-            return
-        w = model._head_master()
-        with torch.cuda.device(model.device):
-            self.m = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
-            self.v = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
-            self.grads = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
-            table = (L.VtdAdamTensor * len(w))()
-            for d, (n, t) in zip(table, w.items()):
-                packed = model._head_packed[n]
-                d.w, d.m, d.v, d.g = (t.data_ptr(), self.m[n].data_ptr(), self.v[n].data_ptr(),
-                                      self.grads[n].data_ptr())
-                d.packed = packed.data_ptr()
-                if t.dim() == 2:
-                    d.kind, d.K, d.N, d.ld = L.ADAM_MATRIX, t.shape[0], t.shape[1], packed.shape[1]
-                else:
-                    d.kind, d.K, d.N, d.ld = L.ADAM_VECTOR, 1, t.numel(), 0
-            need, tiles = ctypes.c_size_t(), ctypes.c_int()
-            L.check(L.lib.vtd_adam_plan_bytes(table, len(w), model.dtype, ctypes.byref(need),
-                                              ctypes.byref(tiles)), "vtd_adam_plan_bytes")
-            self.plan = torch.empty(need.value, dtype=torch.uint8, device=model.device)
-            L.check(L.lib.vtd_adam_plan_upload(table, len(w), model.dtype, self.plan.data_ptr(),
-                                               need.value, L.stream_ptr()), "vtd_adam_plan_upload")
-        self.n, self.tiles = len(w), int(tiles.value)
-
-    def _build_all(self, model):
-        """The vtd_train_step table over every tensor of weight_names(): the device masters
-        `gradients` reads (`_encoder_master()` + `_head_master()`) and, per tensor, the
-        destination `Model._pack` recorded -- the packed operand in the mode's format with
-        vtd_pack_dense's / vtd_pack_vector's grouping, or for a layer whose LayerNorm is folded
-        a persistent fp32 staging operand [N_p][K_p] (allocated here, not at model
-        construction) that the fold job reads after the step."""
-        w = OrderedDict(model._encoder_master())
+        w = OrderedDict(model._encoder_master()) if scope == "all" else OrderedDict()
         w.update(model._head_master())
-        assert list(w) == model.weight_names()
+        assert list(w) == (model.weight_names() if scope == "all" else model.head_weight_names())
+        where = {n: model._train_packed[n] for n in w}
+        folds = model._fold_jobs if any(p["fold"] is not None for p in where.values()) else []
         with torch.cuda.device(model.device):
             self.m = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
             self.v = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
             self.grads = OrderedDict((n, torch.zeros_like(t)) for n, t in w.items())
             self.staging = [torch.zeros(j["shape"], dtype=torch.float32, device=model.device)
-                            for j in model._fold_jobs]
+                            for j in folds]
             table = (L.VtdTrainTensor * len(w))()
             for d, (n, t) in zip(table, w.items()):
-                where = model._train_packed[n]
+                at = where[n]
                 d.w, d.m, d.v, d.g = (t.data_ptr(), self.m[n].data_ptr(), self.v[n].data_ptr(),
                                       self.grads[n].data_ptr())
-                folded = where["fold"] is not None
-                packed = self.staging[where["fold"]] if folded else where["t"]
+                folded = at["fold"] is not None
+                packed = self.staging[at["fold"]] if folded else at["t"]
                 d.packed = packed.data_ptr()
                 d.packed_dtype = L.TRAIN_PACK_F32 if folded else L.TRAIN_PACK_MODE
-                d.row_offset = where["off"]
+                d.row_offset = at["off"]
                 d.constrain, d.rule = 1, L.TRAIN_RULE_DENSE
                 if n.endswith("/embeddings"):
                     # the position embedding (tokens, 1): Keras's sparse Adam path, and the
@@ -204,14 +177,14 @@ class _State:
                 elif n.endswith("/kernel"):
                     # EinsumDense kernels: (D, H, dk) is [D][H dk], grouped along N;
                     # attention_output (H, dk, D) is [H dk][D], grouped along K
-                    w2 = (t.reshape(-1, t.shape[-1]) if t.dim() == 3 and where["kg"] is not None
+                    w2 = (t.reshape(-1, t.shape[-1]) if t.dim() == 3 and at["kg"] is not None
                           else t.reshape(t.shape[0], -1))
                     d.kind, d.K, d.N, d.ld = L.ADAM_MATRIX, w2.shape[0], w2.shape[1], packed.shape[1]
                     kp = d.ld // 3 if model.dtype == L.BF16X3 and not folded else d.ld
-                    d.k_group, d.k_group_p = where["kg"] or d.K, where["kgp"] or kp
+                    d.k_group, d.k_group_p = at["kg"] or d.K, at["kgp"] or kp
                 else:
                     d.kind, d.K, d.N, d.ld = L.ADAM_VECTOR, 1, t.numel(), 0
-                d.n_group, d.n_group_p = where["ng"] or d.N, where["ngp"] or d.N
+                d.n_group, d.n_group_p = at["ng"] or d.N, at["ngp"] or d.N
             need, tiles = ctypes.c_size_t(), ctypes.c_int()
             L.check(L.lib.vtd_train_plan_bytes(table, len(w), model.dtype, ctypes.byref(need),
                                                ctypes.byref(tiles)), "vtd_train_plan_bytes")
@@ -219,9 +192,9 @@ class _State:
             L.check(L.lib.vtd_train_plan_upload(table, len(w), model.dtype, self.plan.data_ptr(),
                                                 need.value, L.stream_ptr()),
                     "vtd_train_plan_upload")
-            if model._fold_jobs:
-                jobs = (L.VtdFoldJob * len(model._fold_jobs))()
-                for j, job, w32 in zip(jobs, model._fold_jobs, self.staging):
+            if folds:
+                jobs = (L.VtdFoldJob * len(folds))()
+                for j, job, w32 in zip(jobs, folds, self.staging):
                     n_p, k_p = job["shape"]
                     j.w32, j.gamma, j.beta = (w32.data_ptr(), job["gamma"].data_ptr(),
                                               job["beta"].data_ptr())
@@ -240,7 +213,7 @@ class _State:
 
 
 def resolve(optimizer):
-    """compile()'s optimizer argument -> an optimizer that can train the head, or raise."""
+    """compile()'s optimizer argument -> an optimizer that can train the model, or raise."""
     if isinstance(optimizer, str) and optimizer.lower() == "adam":
         return Adam()
     if isinstance(optimizer, Adam):
@@ -252,8 +225,8 @@ def resolve(optimizer):
 
 
 class History:
-    """What fit_head returns: `.history["loss"]` holds one float per epoch, `.epoch` the epoch
-    numbers (keras.callbacks.History)."""
+    """What fit and fit_head return: `.history["loss"]` holds one float per epoch, `.epoch` the
+    epoch numbers (keras.callbacks.History)."""
 
     def __init__(self):
         self.history = {"loss": []}
