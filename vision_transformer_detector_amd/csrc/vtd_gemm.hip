@@ -672,28 +672,54 @@ __device__ __forceinline__ void pp2b_sources(PP2Src<AW>& s, const T* A, int lda,
   // (ak0: the split-bf16 wrap aw counts stored K-steps from the row start)
   constexpr int ES = (int)sizeof(T);
   const int ka0 = AW ? 0 : k0;               // the K offset folded into A's base
-  const int64_t ra_bytes = (int64_t)(M - m0) * lda * ES - ES * ka0,
-                rb_bytes = (int64_t)(N - n0) * ldb * ES - ES * k0;
+  // the tile base's element offset inside its operand: one 64-bit product per operand gives the
+  // base pointer and, taken from the operand's size (the same for every workgroup), the records
+  const int64_t oa = (int64_t)m0 * lda + ka0, ob = (int64_t)n0 * ldb + k0;
+  const int64_t ra_bytes = ((int64_t)M * lda - oa) * ES, rb_bytes = ((int64_t)N * ldb - ob) * ES;
+  // min(bytes, 0x7fffffff) of a positive count without a 64-bit compare
+  auto rec32 = [](int64_t b) { return (b >> 31) != 0 ? 0x7fffffff : (int)b; };
   s.ak0 = AW ? k0 * ES / 128 : 0;
   s.aw = AW ? aw : 0;
   // !valid: zero records -- every load out of range (no memory traffic)
-  s.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(A + (int64_t)m0 * lda + ka0), 0,
-                                           valid ? (int)std::min<int64_t>(ra_bytes, 0x7fffffff) : 0,
+  s.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(A + oa), 0, valid ? rec32(ra_bytes) : 0,
                                            0x00020000);
-  s.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(Bt + (int64_t)n0 * ldb + k0), 0,
-                                           valid ? (int)std::min<int64_t>(rb_bytes, 0x7fffffff) : 0,
+  s.rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(Bt + ob), 0, valid ? rec32(rb_bytes) : 0,
                                            0x00020000);
+  // a lane's group row is a wave-uniform first row (group rows (wave * 2 + j) * 8 ..+ 7 are
+  // consecutive tile rows) + prow
   const int prow = lane >> 3, pchunk = (lane & 7) ^ prow;
+  // transposed variant: B groups use swz_t (group row bit 4 = wave & 1 flips chunk bit 2)
+  const int bchunk = TR ? pchunk ^ ((wave & 1) << 2) : pchunk;
+  const int sa = lda * ES, sb = ldb * ES;    // row strides in bytes
+  // A tile wholly inside its operand (every tile of the forward's launches) needs no row clamp:
+  // one per-lane product per operand, independent of the tile's coordinates, and a scalar row
+  // offset per DMA instruction.  Otherwise rows clamp to the operand's last one.
+  if (m0 + BBM <= M) {
+    const int la = prow * sa + pchunk * 16;
 #pragma unroll
-  for (int g = 0; g < 4; ++g)
+    for (int g = 0; g < 2; ++g)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int tr = grp_tile_row(g, (wave * 2 + j) * 8 + prow);
-      // transposed variant: B groups use swz_t (group row bit 4 = wave & 1 flips chunk bit 2)
-      const int bchunk = TR ? pchunk ^ ((wave & 1) << 2) : pchunk;
-      s.off[g][j] = g < 2 ? min(tr, M - 1 - m0) * lda * ES + pchunk * 16
-                          : min(tr, N - 1 - n0) * ldb * ES + bchunk * 16;
-    }
+      for (int j = 0; j < 2; ++j) s.off[g][j] = grp_tile_row(g, (wave * 2 + j) * 8) * sa + la;
+  } else {
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        s.off[g][j] = min(grp_tile_row(g, (wave * 2 + j) * 8) + prow, M - 1 - m0) * sa + pchunk * 16;
+  }
+  if (n0 + BBN <= N) {
+    const int lb = prow * sb + bchunk * 16;
+#pragma unroll
+    for (int g = 2; g < 4; ++g)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) s.off[g][j] = grp_tile_row(g, (wave * 2 + j) * 8) * sb + lb;
+  } else {
+#pragma unroll
+    for (int g = 2; g < 4; ++g)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+        s.off[g][j] = min(grp_tile_row(g, (wave * 2 + j) * 8) + prow, N - 1 - n0) * sb + bchunk * 16;
+  }
 }
 
 template <int G, bool AW>
@@ -819,12 +845,27 @@ __device__ __forceinline__ void pp_mfma32(f32x4 (&acc)[8][4], const bf16x8 (&a)[
 // windows open at 4t-1 (G0) / 4t (G1).  X0,Y0,Y1(t+2) overwrite tile t's, last read by G1 in
 // X(t), retired by 4t+1; the Y(t) windows open at 4t+1 / 4t+2.  RAW: every wave waits for its
 // own DMA before the barrier that opens the readers' window.
-template <bool TR, bool F32 = false, bool AW = true>
-__device__ __forceinline__ void pp2_mainloop_2ph(f32x4 (&acc)[8][4], char* smem,
-                                                 const PP2Src<AW>& src, int nk, int wave, int wm,
-                                                 int wn, int fr, int fg,
-                                                 uint64_t* t_prologue = nullptr) {
-  // prologue: X0,Y0,Y1,X1(0) complete; X0,Y0,Y1(1) in flight
+//
+// Workgroup start.  The kernel issues the prologue's DMA itself (pp2_issue_first: K-tile 0's
+// four groups, then K-tile 1's X0,Y0,Y1, 8 + 6 instructions per wave) as soon as it has the
+// tile's sources, and only then its EX LayerNorm-fold statistics loads (2 per wave, or none)
+// and the accumulator zeroing, which so run while the DMA is in flight.  The statistics loads
+// are vector-memory operations YOUNGER than K-tile 1's DMA, so every counted wait that must
+// leave K-tile 1's DMA in flight leaves them in flight too -- in issue order:
+//   prologue        T0[8] T1'[6] S[EX]                 | vmcnt(6 + EX): T0 landed  (nk = 1: no
+//                                                      | T1', vmcnt(EX))
+//   X(0)            T1'[6] S[EX] X1(1)[2]              | vmcnt(8 + EX): nothing new (as before)
+//   Y(0)            T1'[6] S[EX] X1(1)[2] T2'[6]       | vmcnt(8 + EX): T1' landed
+//   X(1)            S[EX] X1(1)[2] T2'[6] X1(2)[2]     | vmcnt(8): S and X1(1) landed
+// From X(1) on the statistics loads are retired and the counts are the steady state's above.
+// The first K-step is therefore its own compile-time body when EX > 0 and nk > 2 (the LN-fold
+// kernels only).  With nk = 2 the (n1, !n2) body runs as step 0 with the plain counts: its X
+// wait vmcnt(8) then also waits for X0(1), earlier than needed, never later; with nk = 1
+// every wait in the steps is vmcnt(0).  The statistics values themselves are first used in
+// the epilogue, behind the compiler's own wait.
+template <bool AW>
+__device__ __forceinline__ void pp2_issue_first(char* smem, const PP2Src<AW>& src, int nk,
+                                                int wave) {
   pp2_issue<0, AW>(smem, src, wave, 0, 0);
   pp2_issue<2, AW>(smem, src, wave, 0, 0);
   pp2_issue<3, AW>(smem, src, wave, 0, 0);
@@ -833,18 +874,28 @@ __device__ __forceinline__ void pp2_mainloop_2ph(f32x4 (&acc)[8][4], char* smem,
     pp2_issue<0, AW>(smem, src, wave, 1, 1);
     pp2_issue<2, AW>(smem, src, wave, 1, 1);
     pp2_issue<3, AW>(smem, src, wave, 1, 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
+}
+
+// pre: pp2_issue_first, then EX vector-memory loads of the caller's and nothing else
+template <bool TR, bool F32 = false, bool AW = true, int EX = 0>
+__device__ __forceinline__ void pp2_mainloop_2ph(f32x4 (&acc)[8][4], char* smem,
+                                                 const PP2Src<AW>& src, int nk, int wave, int wm,
+                                                 int wn, int fr, int fg,
+                                                 uint64_t* t_prologue = nullptr) {
+  // prologue: X0,Y0,Y1,X1(0) complete; X0,Y0,Y1(1) in flight
+  if (nk > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(6 + EX) : "memory");
+  else asm volatile("s_waitcnt vmcnt(%0)" ::"i"(EX) : "memory");
   pp_barrier();
   if (t_prologue) *t_prologue = __builtin_amdgcn_s_memtime();   // diagnostic stamps only
   if (wm == 1) pp_barrier();                 // stagger G1 by one barrier
   const int ra = wm * 64, rb = wn * 32;
   bf16x8 a[4][2], b0[2][2], b1[2][2];
-  auto step = [&](int kt, auto t1, auto t2) {
+  // ex: the caller's loads still in flight behind K-tile 1's DMA (the first K-step only)
+  auto step = [&](int kt, auto t1, auto t2, auto ex) {
     const char* st = smem + (kt & 1) * BSTAGE;
     constexpr bool n1 = decltype(t1)::value, n2 = decltype(t2)::value;
+    constexpr int W8 = 8 + decltype(ex)::value;
     // ---- X
     pp_load_a(a, st + 0 * 16384, ra, fr, fg);
     if constexpr (TR) {
@@ -856,7 +907,7 @@ __device__ __forceinline__ void pp2_mainloop_2ph(f32x4 (&acc)[8][4], char* smem,
     }
     if constexpr (n1) {
       pp2_issue<1, AW>(smem, src, wave, kt + 1, (kt + 1) & 1);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(W8) : "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -869,7 +920,7 @@ __device__ __forceinline__ void pp2_mainloop_2ph(f32x4 (&acc)[8][4], char* smem,
       pp2_issue<0, AW>(smem, src, wave, kt + 2, kt & 1);
       pp2_issue<2, AW>(smem, src, wave, kt + 2, kt & 1);
       pp2_issue<3, AW>(smem, src, wave, kt + 2, kt & 1);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"i"(W8) : "memory");
     } else {
       // last K-step: every LDS read retired before the barrier, so that G0, released
       // into its epilogue by the next one, cannot overwrite a stage G1 is still reading
@@ -881,10 +932,14 @@ __device__ __forceinline__ void pp2_mainloop_2ph(f32x4 (&acc)[8][4], char* smem,
     // runs beside G1's last MFMA cluster instead of waiting for it (no re-align barrier)
     if (n1 || n2 || wm == 0) pp_barrier();
   };
+  constexpr std::integral_constant<int, 0> ex0{};
   int kt = 0;
-  for (; kt + 2 < nk; ++kt) step(kt, std::true_type{}, std::true_type{});
-  if (kt + 1 < nk) step(kt++, std::true_type{}, std::false_type{});
-  step(kt, std::false_type{}, std::false_type{});
+  if constexpr (EX > 0) {
+    if (nk > 2) step(kt++, std::true_type{}, std::true_type{}, std::integral_constant<int, EX>{});
+  }
+  for (; kt + 2 < nk; ++kt) step(kt, std::true_type{}, std::true_type{}, ex0);
+  if (kt + 1 < nk) step(kt++, std::true_type{}, std::false_type{}, ex0);
+  step(kt, std::false_type{}, std::false_type{}, ex0);
 }
 
 // Epilogue of the transposed variant, full tiles: lane (fr, fg) of wave (wm, wn) holds,
@@ -1070,14 +1125,31 @@ __global__ __launch_bounds__(BNT) void gemm_tn_bf16_pp2_kernel(
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
+  // Workgroup start: what the first DMA needs and nothing else -- the tile's coordinates, the
+  // two buffer resources, the per-lane offsets -- then K-tiles 0 and 1 are issued; the
+  // statistics loads, the accumulator zeroing and the split-K output base follow and run while
+  // the DMA is in flight (wait accounting: pp2_mainloop_2ph)
+  uint64_t ts[4] = {0, 0, 0, 0};
+  [[maybe_unused]] uint64_t rt0 = 0;
+  if constexpr ((DG & 16) != 0) {
+    ts[0] = __builtin_amdgcn_s_memtime();
+    rt0 = __builtin_amdgcn_s_memrealtime();
+  }
+  // every kernel argument the start reads, requested up front (left to itself the compiler
+  // loads them where first used: four dependent scalar-load round trips before the DMA; so
+  // two, the second only because the compiler reuses a register of the first batch)
+  asm volatile("" ::"s"(M), "s"(N), "s"(K), "s"(A), "s"(lda), "s"(Bt), "s"(ldb), "s"(tiles_m),
+               "s"(tiles_n), "s"(ksplit), "s"(e.to.tiles_n), "s"(e.to.grouped), "s"(e.aw));
   const int nt = tiles_m * tiles_n, nwg = nt * ksplit;
   const int bid = blockIdx.x;
 #if VTD_DIAG
   if (e.dsl > 0 && bid < 256 && ((bid >> 3) & 1))
     for (int i = 0; i < e.dsl; ++i) __builtin_amdgcn_s_sleep(8);
 #endif
+  // XCD remap, XCD x taking nwg / 8 consecutive workgroups and the first nwg % 8 XCDs one
+  // more: x * (q + 1) for x < r, r * (q + 1) + (x - r) * q otherwise, without the branch
   const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int v = xcd * q + min(xcd, r) + (bid >> 3);
   // one K range (the forward's launches): no division by the tile count or split count
   const int split = ksplit > 1 ? v / nt : 0, tile = v - split * nt;
   int tm, tn;
@@ -1085,13 +1157,23 @@ __global__ __launch_bounds__(BNT) void gemm_tn_bf16_pp2_kernel(
   const int m0 = tm * BBM, n0 = tn * BBN;
   const int nk_all = K / 64, nks = ksplit > 1 ? (nk_all + ksplit - 1) / ksplit : nk_all;
   const int k0 = split * nks, nk = min(nks, nk_all - k0);   // host: every split non-empty
-  if (ksplit > 1) e.out = static_cast<float*>(e.out) + split * e.split_stride;
   PP2Src<pp2_wraps(EPI)> src;
   pp2b_sources<TR>(src, A, lda, M, Bt, ldb, N, m0, n0, wave, lane, k0 * 64, true, e.aw);
-  // LayerNorm-fold row statistics of the wave's 128 rows: issued before the K loop (the
-  // oldest vector-memory op, so the loop's counted waits retire it), used in the epilogue
+  // the two-phase loop's prologue DMA from here; the four-phase loop (A/B and diagnostic builds)
+  // issues its own, behind the statistics loads
+  constexpr bool kEarly = VTD_PP2_PH == 2 && (DG & 32) == 0;
+  constexpr bool kLnf = EPI != EPI_GENERIC && (EPI & EPI_LNF) != 0;
+  if constexpr (kEarly) {
+    pp2_issue_first(smem, src, nk, wave);
+    // nothing below moves above the DMA: the waits count the statistics loads as younger
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");
+  }
+  if (ksplit > 1) e.out = static_cast<float*>(e.out) + split * e.split_stride;
+  // LayerNorm-fold row statistics of the wave's 128 rows (two loads per wave), used in the
+  // epilogue
   float2 lst[2] = {float2{0.f, 0.f}, float2{0.f, 0.f}};
-  if constexpr (EPI != EPI_GENERIC && (EPI & EPI_LNF) != 0) {
+  if constexpr (kLnf) {
     lst[0] = e.lnstat[min(m0 + wm * 128 + lane, M - 1)];
     lst[1] = e.lnstat[min(m0 + wm * 128 + 64 + lane, M - 1)];
   }
@@ -1099,16 +1181,16 @@ __global__ __launch_bounds__(BNT) void gemm_tn_bf16_pp2_kernel(
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) {
+      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      // zeroed here, ahead of the prologue's wait (the compiler otherwise sinks the 128 moves
+      // behind the prologue barrier, in front of the first MFMA)
+      if constexpr (kEarly) asm volatile("" : "+v"(acc[i][j]));
+    }
   const int fr = lane & 15, fg = lane >> 4;
-  uint64_t ts[4] = {0, 0, 0, 0};
-  [[maybe_unused]] uint64_t rt0 = 0;
-  if constexpr ((DG & 16) != 0) {
-    ts[0] = __builtin_amdgcn_s_memtime();
-    rt0 = __builtin_amdgcn_s_memrealtime();
-  }
-  if constexpr (VTD_PP2_PH == 2 && (DG & 32) == 0)
-    pp2_mainloop_2ph<TR>(acc, smem, src, nk, wave, wm, wn, fr, fg, (DG & 16) ? &ts[1] : nullptr);
+  if constexpr (kEarly)
+    pp2_mainloop_2ph<TR, false, pp2_wraps(EPI), kLnf ? 2 : 0>(acc, smem, src, nk, wave, wm, wn, fr,
+                                                             fg, (DG & 16) ? &ts[1] : nullptr);
   else
     pp2_mainloop<TR, false, (DG & 32) != 0>(acc, smem, src, nk, wave, wm, wn, fr, fg,
                                              (DG & 16) ? &ts[1] : nullptr);
