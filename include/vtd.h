@@ -682,6 +682,54 @@ int vtd_attention_backward(const void* qkv_dev, const void* o_dev, const void* d
                            int ldo, int lddo, float scale, void* dqkv_dev, int lddqkv, int dtype,
                            void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---- dropout (an addition to ABI 17; DESIGN.md "Dropout")
+ * Keras Dropout semantics: a kept value is multiplied by inv_keep, a dropped one is +0.  The
+ * mask is generated inside the kernels by Philox4x32-10 and never stored; a mask bit is a pure
+ * function of (seed, step, site, logical index) -- (row, column) of the unpadded [rows][N]
+ * activation at an elementwise site, (image, head, query, key) at an attention site -- and of
+ * nothing else (no leading dimension, padding, batch size, kernel variant or backward pass).
+ * rate is realised as thr / 65536, thr = round(rate * 65536) <= 65535; inv_keep is the fp32
+ * rounding of 1 / (1 - thr / 65536), exactly 2 at rate 0.5.  TensorFlow's random stream is not
+ * reproduced: the distribution is the reference's, the bits are this library's.
+ * Every entry below returns VTD_ERR_INVALID_ARG before any device call for a NULL vtd_dropout
+ * or a rate outside [0, 1) (NaN included); rate == 0 takes the existing entry's path (the same
+ * launches, the same bits). */
+typedef struct vtd_dropout { uint64_t seed, step; uint32_t site; float rate; } vtd_dropout;
+/* the mask as bytes (1 = kept), through the kernels' own device function: out [rows][ldo]
+ * (columns < N written) and out [B][heads][N][N] */
+int vtd_dropout_mask(const vtd_dropout* drop, int64_t rows, int N, uint8_t* out_dev, int ldo,
+                     void* stream);
+int vtd_dropout_mask_attention(const vtd_dropout* drop, int B, int heads, int N, uint8_t* out_dev,
+                               void* stream);
+/* y = drop(x), fp32 [rows][ldx] -> fp32 [rows][ldy], columns < N: y = fp32(x * inv_keep) or +0.
+ * The layer's gradient is the same call on the incoming gradient. */
+int vtd_dropout_apply(const vtd_dropout* drop, const float* x_dev, int ldx, int64_t rows, int N,
+                      float* y_dev, int ldy, void* stream);
+/* vtd_act_forward / vtd_act_grad with the mask of (row, column): a = drop(act(z)) and
+ * gz = act'(z) * (m * inv_keep * ga): one fp32 multiply by inv_keep before the single rounding
+ * into the stored form; pad columns zero as before. */
+int vtd_act_forward_dropout(const float* z_dev, int64_t rows, int N, int ldz, int act, void* a_dev,
+                            int lda, int dtype, void* stream, const vtd_dropout* drop);
+int vtd_act_grad_dropout(const float* z_dev, int ldz, const float* ga_dev, int ldga, int64_t rows,
+                         int N, int act, void* gz_dev, int ldgz, int dtype, void* stream,
+                         const vtd_dropout* drop);
+/* vtd_attention_train / vtd_attention_backward with dropout on the attention probabilities
+ * (the MultiHeadAttention `dropout`): O = ((P o M) inv_keep) V.  The softmax statistics, the
+ * normalisation and lse_dev are those of the undropped softmax (lse_dev has vtd_attention_train's
+ * bits); only the operand of the P V product is masked.  Backward, from the dropped O:
+ *   delta_i = sum_d dO_id O_id (unchanged: sum_j P_ij dP_ij = dO_i . O_i still holds),
+ *   dP = M inv_keep (dO V^T), dS = P (dP - delta) scale with the unmasked P,
+ *   dV = (P o M inv_keep)^T dO, dK, dQ from dS as before.
+ * The same (seed, step, site) as the forward regenerates its mask; nothing N x N is stored and
+ * the workspace is vtd_attention_backward_workspace_bytes.  Bit-identical from run to run. */
+int vtd_attention_train_dropout(const void* qkv_dev, int B, int N, int heads, int dkp, int ldqkv,
+                                float scale, void* out_dev, int ldo, float* lse_dev, int dtype,
+                                void* stream, const vtd_dropout* drop);
+int vtd_attention_backward_dropout(const void* qkv_dev, const void* o_dev, const void* do_dev,
+                                   const float* lse_dev, int B, int N, int heads, int dkp,
+                                   int ldqkv, int ldo, int lddo, float scale, void* dqkv_dev,
+                                   int lddqkv, int dtype, void* ws_dev, size_t ws_bytes,
+                                   void* stream, const vtd_dropout* drop);
 /* ---- LayerNorm backward (an addition to ABI 17; DESIGN.md "Encoder block backward")
  * The gradients of keras LayerNormalization(axis=-1) given d loss / d y, all fp32 (in training
  * the residual stream and its gradient are fp32 in every operand mode, so there is no dtype):
@@ -775,6 +823,21 @@ int vtd_encoder_block_backward(const vtd_block_dims* dims, const vtd_block_param
                                const float* x_dev, const float* dy_dev, float* y_dev,
                                const vtd_block_grads* grads, void* ws, size_t ws_bytes,
                                void* stream);
+
+/* vtd_encoder_block_backward with the reference's `dropout` in the block
+ * (vtd.py:359-369, 404-405): site_base is the attention probabilities' site, site_base + 1 + j
+ * the Dropout after MLP layer j's activation -- the last layer's too, before the residual add
+ * (y = x1 + drop(act(z_last))).  The backward's recomputed training forward regenerates the
+ * forward's masks from the same (seed, step, site_base).  Same workspace
+ * (vtd_encoder_block_backward_workspace_bytes), same checks; in addition VTD_ERR_INVALID_ARG
+ * before any device call for a NULL drop, a rate outside [0, 1) or site_base + mlp_quantities
+ * beyond 32 bits.  rate == 0: vtd_encoder_block_backward's launches and bits.  Blocks chained in
+ * one model take distinct site_base values, i * (1 + mlp_quantities) for block i. */
+typedef struct vtd_block_dropout { uint64_t seed, step; uint32_t site_base; float rate; } vtd_block_dropout;
+int vtd_encoder_block_backward_dropout(const vtd_block_dims* dims, const vtd_block_params* params,
+                                       const float* x_dev, const float* dy_dev, float* y_dev,
+                                       const vtd_block_grads* grads, void* ws, size_t ws_bytes,
+                                       void* stream, const vtd_block_dropout* drop);
 
 /* ---- patch embedding backward (additions to ABI 17; DESIGN.md "Whole-model gradients")
  * The stem of the reference (transformer_preprocessor, vtd.py:271-307):

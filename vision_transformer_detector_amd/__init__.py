@@ -40,6 +40,7 @@ from .metrics import MeanAveragePrecision, iou_calculator  # noqa: F401
 from .loss import (ciou_calculator, diagonal_calculator, get_label_arrays,  # noqa: F401
                    loss_and_grad, loss_components, my_custom_loss)
 from .attention import attention_core  # noqa: F401
+from .dropout import dropout, dropout_mask  # noqa: F401
 from .layernorm import layer_norm  # noqa: F401
 from .encoder import encoder_block  # noqa: F401
 from .stem import patch_embedding  # noqa: F401
@@ -52,5 +53,6 @@ __all__ = ["Constants", "Model", "create_vision_transformer_detector",
            "MeanAveragePrecision", "iou_calculator", "get_image_tensors",
            "my_custom_loss", "loss_components", "loss_and_grad", "ciou_calculator",
            "diagonal_calculator", "get_label_arrays", "optimizers",
-           "learning_rate_step_decay", "attention_core", "layer_norm", "encoder_block",
+           "learning_rate_step_decay", "attention_core", "dropout", "dropout_mask", "layer_norm",
+           "encoder_block",
            "patch_embedding", "enable_device_kernel_arguments"]

@@ -117,6 +117,18 @@ class VtdBlockGrads(ctypes.Structure):
     _fields_ = VtdBlockParams._fields_ + [("dx", c_void_p)]
 
 
+class VtdDropout(ctypes.Structure):
+    """vtd_dropout: the mask is a function of (seed, step, site, logical index) alone."""
+    _fields_ = [("seed", ctypes.c_uint64), ("step", ctypes.c_uint64), ("site", ctypes.c_uint32),
+                ("rate", c_float)]
+
+
+class VtdBlockDropout(ctypes.Structure):
+    """vtd_block_dropout: site_base the attention probabilities, site_base + 1 + j MLP layer j."""
+    _fields_ = [("seed", ctypes.c_uint64), ("step", ctypes.c_uint64),
+                ("site_base", ctypes.c_uint32), ("rate", c_float)]
+
+
 class VtdStemDims(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "H", "W", "C", "patch", "d", "dtype")]
 
@@ -247,6 +259,23 @@ SIGNATURES = {
     "vtd_attention_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                        c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                        c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "vtd_dropout_mask": (c_int, [ctypes.POINTER(VtdDropout), c_int64, c_int, c_void_p, c_int,
+                                 c_void_p]),
+    "vtd_dropout_mask_attention": (c_int, [ctypes.POINTER(VtdDropout), c_int, c_int, c_int,
+                                           c_void_p, c_void_p]),
+    "vtd_dropout_apply": (c_int, [ctypes.POINTER(VtdDropout), c_void_p, c_int, c_int64, c_int,
+                                  c_void_p, c_int, c_void_p]),
+    "vtd_act_forward_dropout": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int,
+                                        c_int, c_void_p, ctypes.POINTER(VtdDropout)]),
+    "vtd_act_grad_dropout": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int,
+                                     c_void_p, c_int, c_int, c_void_p, ctypes.POINTER(VtdDropout)]),
+    "vtd_attention_train_dropout": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                            c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                            ctypes.POINTER(VtdDropout)]),
+    "vtd_attention_backward_dropout": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                               c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                               c_void_p, c_int, c_int, c_void_p, c_size_t,
+                                               c_void_p, ctypes.POINTER(VtdDropout)]),
     "vtd_layernorm_backward_workspace_bytes": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "vtd_layernorm_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                        c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p,
@@ -257,6 +286,12 @@ SIGNATURES = {
                                            ctypes.POINTER(VtdBlockParams), c_void_p, c_void_p,
                                            c_void_p, ctypes.POINTER(VtdBlockGrads), c_void_p,
                                            c_size_t, c_void_p]),
+    "vtd_encoder_block_backward_dropout": (c_int, [ctypes.POINTER(VtdBlockDims),
+                                                   ctypes.POINTER(VtdBlockParams), c_void_p,
+                                                   c_void_p, c_void_p,
+                                                   ctypes.POINTER(VtdBlockGrads), c_void_p,
+                                                   c_size_t, c_void_p,
+                                                   ctypes.POINTER(VtdBlockDropout)]),
     "vtd_stem_backward_workspace_bytes": (c_int, [ctypes.POINTER(VtdStemDims),
                                                   ctypes.POINTER(c_size_t)]),
     "vtd_stem_backward": (c_int, [ctypes.POINTER(VtdStemDims), ctypes.POINTER(VtdStemParams),

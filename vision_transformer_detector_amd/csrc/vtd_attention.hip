@@ -268,11 +268,15 @@ struct AttnBf16Cfg {
 // through that XCD's L2 once instead of once per XCD from beyond it.
 // LSE (vtd_attention_train): the same kernel also writes lse[b][h][q] = ln sum_k exp(score),
 // natural units, from the statistics it already holds; O is computed by the same instructions.
-template <int DKP, int NWG, bool MX8 = false, bool LSE = false>
-__global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void attention_bf16_kernel(
+// DROP (vtd_attention_train_dropout): O = ((P o M) inv_keep) V.  Only the operand of the P V
+// products is masked (vtd_philox.h: one Philox block per four keys of the lane's query); the
+// running max, the row sum -- the fp32 sum, or with SUMMFMA the ones-block product of the
+// UNMASKED bf16 P -- the normalisation and the LSE are the undropped softmax's, bit for bit.
+template <int DKP, int NWG, bool MX8, bool LSE, bool DROP>
+__device__ __forceinline__ void attention_bf16_body(
     const bf16_t* __restrict__ qkv, int N, int heads, int ldqkv, float scale_log2,
     bf16_t* __restrict__ out, int ldo, uint8_t* __restrict__ s8, int64_t s_rows, int nqb,
-    int xcd_remap, float* __restrict__ lse = nullptr) {
+    int xcd_remap, float* __restrict__ lse, DropKey dk) {
   using C = AttnBf16Cfg<DKP>;
   typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -392,6 +396,20 @@ __global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void
       // ragged: N = 196 leaves 4 keys in it, one block)
       const int nkb = LAST ? min(2, (N - kv0 + 31) >> 5) : 2;
       const bool ragged = LAST && kv0 + C::KC > N;
+      // DROP: the chunk's keep bits first, while the score registers are not yet live (bit
+      // 16 kb + 4 g + j: key kv0 + 32 kb + 8 g + 4 half + j of the lane's query)
+      uint32_t keep = 0;
+      if constexpr (DROP) {
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+          if (kb < nkb) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+              keep |= drop_keep4_keys(dk, b, h, q0 + col, kv0 + kb * 32 + 8 * g + 4 * half)
+                      << (16 * kb + 4 * g);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      }
       f32x16 s[2];
       const f32x16 zero = {};
 #pragma unroll
@@ -515,6 +533,17 @@ __global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void
                               (int)pack_bf16x2(s[kb][8 * st + 2], s[kb][8 * st + 3]),
                               (int)pack_bf16x2(s[kb][8 * st + 4], s[kb][8 * st + 5]),
                               (int)pack_bf16x2(s[kb][8 * st + 6], s[kb][8 * st + 7])});
+            bf16x8 pv = pb;              // the P V operand: masked and scaled with DROP
+            if constexpr (DROP) {
+              float m[8];
+#pragma unroll
+              for (int j = 0; j < 8; ++j)
+                m[j] = (keep >> (16 * kb + 8 * st + j)) & 1u ? s[kb][8 * st + j] * dk.inv_keep
+                                                             : 0.f;
+              pv = __builtin_bit_cast(
+                  bf16x8, i32x4{(int)pack_bf16x2(m[0], m[1]), (int)pack_bf16x2(m[2], m[3]),
+                                (int)pack_bf16x2(m[4], m[5]), (int)pack_bf16x2(m[6], m[7])});
+            }
             const int key0 = kb * 32 + 16 * st + tr_key;
 #pragma unroll
             for (int db = 0; db < C::DB; ++db) {
@@ -523,7 +552,7 @@ __global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void
               const bf16x4 hi =
                   __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(va + 8 * C::VS));
               const bf16x8 a = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-              o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pb, o[db], 0, 0, 0);
+              o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, pv, o[db], 0, 0, 0);
             }
             if constexpr (SUMMFMA) osum = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_ones, pb, osum, 0, 0, 0);
           }
@@ -604,6 +633,25 @@ __global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void
                        pack_bf16x2(o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv)};
       *reinterpret_cast<uint2*>(op + d) = v;
     }
+}
+
+template <int DKP, int NWG, bool MX8 = false, bool LSE = false>
+__global__ __launch_bounds__(64 * NWG, NWG == 4 ? (DKP == 128 ? 2 : 3) : 2) void attention_bf16_kernel(
+    const bf16_t* __restrict__ qkv, int N, int heads, int ldqkv, float scale_log2,
+    bf16_t* __restrict__ out, int ldo, uint8_t* __restrict__ s8, int64_t s_rows, int nqb,
+    int xcd_remap, float* __restrict__ lse = nullptr) {
+  attention_bf16_body<DKP, NWG, MX8, LSE, false>(qkv, N, heads, ldqkv, scale_log2, out, ldo, s8,
+                                                 s_rows, nqb, xcd_remap, lse, DropKey{});
+}
+// the training forward with dropout: launch bounds of its own (DESIGN.md "Dropout")
+template <int DKP, int NWG>
+__global__ __launch_bounds__(64 * NWG, NWG == 4 ? 2 : 1) void attention_bf16_drop_kernel(
+    const bf16_t* __restrict__ qkv, int N, int heads, int ldqkv, float scale_log2,
+    bf16_t* __restrict__ out, int ldo, int nqb, float* __restrict__ lse, uint32_t dk0,
+    uint32_t dk1, uint32_t dthr, float inv_keep) {
+  const DropKey dk{dk0, dk1, dthr, inv_keep};
+  attention_bf16_body<DKP, NWG, false, true, true>(qkv, N, heads, ldqkv, scale_log2, out, ldo,
+                                                   nullptr, 0, nqb, 1, lse, dk);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1462,10 +1510,12 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& h
                                         (int)pack_lo_bf16x2(b[2], b[3], h3)});
 }
 
-template <int DKP, int NWG, int KC = 64, int MINB = 1, bool LSE = false>
-__global__ __launch_bounds__(64 * NWG, MINB) void attention_x3_kernel(
+// DROP: as in attention_bf16_body -- the fp32 P is masked and scaled just before it is split
+// into the P V operand; statistics and LSE unmasked.
+template <int DKP, int NWG, int KC, bool LSE, bool DROP>
+__device__ __forceinline__ void attention_x3_body(
     const float* __restrict__ qkv, int N, int heads, int ldqkv, float scale_log2,
-    bf16_t* __restrict__ out, int ldo, int nqb, float* __restrict__ lse = nullptr) {
+    bf16_t* __restrict__ out, int ldo, int nqb, float* __restrict__ lse, DropKey dk) {
   using C = AttnX3Cfg<DKP, KC>;
   typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1551,6 +1601,18 @@ __global__ __launch_bounds__(64 * NWG, MINB) void attention_x3_kernel(
       const char* vl = kl + C::KC * C::KS;
       const int nkb = LAST ? min(C::NKB, (N - kv0 + 31) >> 5) : C::NKB;
       const bool ragged = LAST && kv0 + C::KC > N;
+      uint32_t keep = 0;       // DROP: as in attention_bf16_body
+      if constexpr (DROP) {
+#pragma unroll
+        for (int kb = 0; kb < C::NKB; ++kb)
+          if (kb < nkb) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+              keep |= drop_keep4_keys(dk, b, h, q0 + col, kv0 + kb * 32 + 8 * g + 4 * half)
+                      << (16 * kb + 4 * g);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      }
       f32x16 s[C::NKB];
 #pragma unroll
       for (int kb = 0; kb < C::NKB; ++kb) {
@@ -1619,6 +1681,13 @@ __global__ __launch_bounds__(64 * NWG, MINB) void attention_x3_kernel(
 #pragma unroll
           for (int st = 0; st < 2; ++st) {
             bf16x8 ph, pl;
+            if constexpr (DROP) {
+#pragma unroll
+              for (int j = 0; j < 8; ++j) {
+                const int r = 8 * st + j;
+                s[kb][r] = (keep >> (16 * kb + r)) & 1u ? s[kb][r] * dk.inv_keep : 0.f;
+              }
+            }
             split8(f32x4{s[kb][8 * st + 0], s[kb][8 * st + 1], s[kb][8 * st + 2], s[kb][8 * st + 3]},
                    f32x4{s[kb][8 * st + 4], s[kb][8 * st + 5], s[kb][8 * st + 6], s[kb][8 * st + 7]},
                    ph, pl);
@@ -1698,6 +1767,63 @@ __global__ __launch_bounds__(64 * NWG, MINB) void attention_x3_kernel(
       *reinterpret_cast<uint2*>(op + d) = hv;
       *reinterpret_cast<uint2*>(op + P + d) = lv;
     }
+}
+
+template <int DKP, int NWG, int KC = 64, int MINB = 1, bool LSE = false>
+__global__ __launch_bounds__(64 * NWG, MINB) void attention_x3_kernel(
+    const float* __restrict__ qkv, int N, int heads, int ldqkv, float scale_log2,
+    bf16_t* __restrict__ out, int ldo, int nqb, float* __restrict__ lse = nullptr) {
+  attention_x3_body<DKP, NWG, KC, LSE, false>(qkv, N, heads, ldqkv, scale_log2, out, ldo, nqb, lse,
+                                              DropKey{});
+}
+template <int DKP, int NWG, int KC, int MINB>
+__global__ __launch_bounds__(64 * NWG, MINB) void attention_x3_drop_kernel(
+    const float* __restrict__ qkv, int N, int heads, int ldqkv, float scale_log2,
+    bf16_t* __restrict__ out, int ldo, int nqb, float* __restrict__ lse, uint32_t dk0,
+    uint32_t dk1, uint32_t dthr, float inv_keep) {
+  const DropKey dk{dk0, dk1, dthr, inv_keep};
+  attention_x3_body<DKP, NWG, KC, true, true>(qkv, N, heads, ldqkv, scale_log2, out, ldo, nqb, lse,
+                                              dk);
+}
+
+template <int DKP, int KC, int MINB>
+int launch_x3_drop(const void* qkv, int B, int N, int heads, int ldqkv, float scale, void* out,
+                   int ldo, hipStream_t stream, float* lse, const DropKey& dk) {
+  using C = AttnX3Cfg<DKP, KC>;
+  constexpr int NWG = 8;
+  constexpr int LDS = std::max(2 * C::BUF, DKP == 64 ? NWG * 2 * 32 * 144 : 0);
+  const int nq = (N + 31) / 32, nqb = (nq + NWG - 1) / NWG;
+  VTD_CHECK_ARG((int64_t)nqb * heads * B < INT32_MAX, "attention: grid too large");
+  static std::once_flag once[kMaxDevices];
+  once_per_device(once, [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_x3_drop_kernel<DKP, NWG, KC, MINB>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  });
+  hipLaunchKernelGGL((attention_x3_drop_kernel<DKP, NWG, KC, MINB>), dim3(nqb * heads * B),
+                     dim3(64 * NWG), LDS, stream, static_cast<const float*>(qkv), N, heads, ldqkv,
+                     scale * 1.4426950408889634f, static_cast<bf16_t*>(out), ldo, nqb, lse, dk.k0,
+                     dk.k1, dk.thr, dk.inv_keep);
+  VTD_LAUNCH_CHECK("attention_x3_dropout");
+  return VTD_OK;
+}
+
+template <int DKP, int NWG>
+int launch_bf16_drop(const void* qkv, int B, int N, int heads, int ldqkv, float scale, void* out,
+                     int ldo, hipStream_t stream, float* lse, const DropKey& dk) {
+  using C = AttnBf16Cfg<DKP>;
+  const int nq = (N + 31) / 32, nqb = (nq + NWG - 1) / NWG;
+  VTD_CHECK_ARG((int64_t)nqb * heads * B < INT32_MAX, "attention: grid too large");
+  static std::once_flag once[kMaxDevices];
+  once_per_device(once, [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_bf16_drop_kernel<DKP, NWG>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 2 * C::BUF);
+  });
+  hipLaunchKernelGGL((attention_bf16_drop_kernel<DKP, NWG>), dim3(nqb * heads * B), dim3(64 * NWG),
+                     2 * C::BUF, stream, static_cast<const bf16_t*>(qkv), N, heads, ldqkv,
+                     scale * 1.4426950408889634f, static_cast<bf16_t*>(out), ldo, nqb, lse, dk.k0,
+                     dk.k1, dk.thr, dk.inv_keep);
+  VTD_LAUNCH_CHECK("attention_bf16_dropout");
+  return VTD_OK;
 }
 
 template <int DKP, int KC = 64, int MINB = 1, bool LSE = false>
@@ -1845,6 +1971,51 @@ int attention_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqk
 // vtd_attention_train: the streaming kernels vtd_attention runs (VTD_BF16X3 at the default;
 // VTD_BF16 as under VTD_KNOB_ATTN_VARIANT 2: 4 waves up to N = 128, else 8), instantiated with
 // LSE, so O has the same bits and lse comes from the same statistics.
+int attention_train_drop_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
+                                float scale, void* out, int ldo, float* lse, int dtype,
+                                const DropKey& dk, hipStream_t stream) {
+  VTD_CHECK_ARG(qkv && out && lse, "attention_train_dropout: null pointer");
+  VTD_CHECK_ARG(B > 0 && N > 0 && heads > 0, "attention_train_dropout: bad B/N/heads");
+  VTD_CHECK_ARG(dkp == 32 || dkp == 64 || dkp == 128,
+                "attention_train_dropout: dkp must be 32/64/128");
+  VTD_CHECK_ARG(scale > 0 && std::isfinite(scale),
+                "attention_train_dropout: scale must be positive and finite");
+  if (dtype != VTD_BF16 && dtype != VTD_BF16X3)
+    return fail(VTD_ERR_UNSUPPORTED,
+                "attention_train_dropout: dtype must be VTD_BF16 or VTD_BF16X3");
+  const bool x3 = dtype == VTD_BF16X3;
+  VTD_CHECK_ARG(!x3 || ldo % 2 == 0,
+                "attention_train_dropout: a split-bf16 output needs ldo % 2 == 0");
+  const int owidth = x3 ? ldo / 2 : ldo;
+  VTD_CHECK_ARG(ldqkv >= 3 * heads * dkp && owidth >= heads * dkp,
+                "attention_train_dropout: leading dimensions too small");
+  VTD_CHECK_ARG(ldqkv % 8 == 0 && owidth % 8 == 0,
+                "attention_train_dropout: ld must be multiple of 8");
+  ProfScope ps(stream, PROF_ATTN, 4.0 * B * heads * (double)N * N * dkp);
+  // the variants vtd_attention_train picks (its knob included), so that the statistics and the
+  // LSE are computed by the same instructions
+  if (x3) {
+    if (dkp == 32)
+      return launch_x3_drop<32, 64, 1>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk);
+    if (dkp == 64 && knob(VTD_KNOB_ATTN_VARIANT) != 10)
+      return launch_x3_drop<64, 32, 2>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk);
+    if (dkp == 64)
+      return launch_x3_drop<64, 64, 1>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk);
+    return launch_x3_drop<128, 64, 1>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk);
+  }
+#define VTD_TRAIN_DROP(D, W) \
+  launch_bf16_drop<D, W>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk)
+  if (N > 128) {
+    if (dkp == 32) return VTD_TRAIN_DROP(32, 8);
+    if (dkp == 64) return VTD_TRAIN_DROP(64, 8);
+    return VTD_TRAIN_DROP(128, 8);
+  }
+  if (dkp == 32) return VTD_TRAIN_DROP(32, 4);
+  if (dkp == 64) return VTD_TRAIN_DROP(64, 4);
+  return VTD_TRAIN_DROP(128, 4);
+#undef VTD_TRAIN_DROP
+}
+
 int attention_train_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
                            float scale, void* out, int ldo, float* lse, int dtype,
                            hipStream_t stream) {
@@ -1936,4 +2107,18 @@ extern "C" int vtd_attention_train(const void* qkv_dev, int B, int N, int heads,
                                    float* lse_dev, int dtype, void* stream) {
   return vtd::attention_train_launch(qkv_dev, B, N, heads, dkp, ldqkv, scale, out_dev, ldo,
                                      lse_dev, dtype, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vtd_attention_train_dropout(const void* qkv_dev, int B, int N, int heads, int dkp,
+                                           int ldqkv, float scale, void* out_dev, int ldo,
+                                           float* lse_dev, int dtype, void* stream,
+                                           const vtd_dropout* drop) {
+  vtd::DropKey dk;
+  bool on;
+  if (int rc = vtd::drop_prepare("vtd_attention_train_dropout", drop, &dk, &on)) return rc;
+  if (!on)
+    return vtd::attention_train_launch(qkv_dev, B, N, heads, dkp, ldqkv, scale, out_dev, ldo,
+                                       lse_dev, dtype, static_cast<hipStream_t>(stream));
+  return vtd::attention_train_drop_launch(qkv_dev, B, N, heads, dkp, ldqkv, scale, out_dev, ldo,
+                                          lse_dev, dtype, dk, static_cast<hipStream_t>(stream));
 }

@@ -140,12 +140,16 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(
 // forward's: the blocks of one (image, head) share an XCD and stream the same tiles through
 // its L2.  Rows beyond N are clamped on read (nothing is read past row B N - 1); streamed
 // rows beyond N get P = 0, stationary rows beyond N are not written.
-template <int DKP, bool X3, bool KV>
-__global__ __launch_bounds__(64 * bwd_waves(DKP, X3), bwd_min_blocks(DKP, X3)) void attn_bwd_kernel(
-    const void* __restrict__ qkv_, int ldqkv, const void* __restrict__ do_, int lddo,
-    const float* __restrict__ lse, const float* __restrict__ delta, int N, int heads,
-    float scale_log2, float scale, bf16_t* __restrict__ dqkv, int lddqkv, int nblk,
-    float* __restrict__ rinv) {
+// DROP (vtd_attention_backward_dropout): the forward's mask M of (b, h, query, key) is
+// regenerated per tile (vtd_philox.h; four keys of a query per Philox block in the Q pass, four
+// queries of a key from two blocks in the KV pass): dP = M inv_keep (dO V^T) -- so -delta
+// joins after the masking instead of as the initial accumulator -- dS = P (dP - delta) with the
+// unmasked P, and the dV product takes P o M inv_keep.  The row-sum sweep stays unmasked.
+template <int DKP, bool X3, bool KV, bool DROP>
+__device__ __forceinline__ void attn_bwd_body(
+    const void* qkv_, int ldqkv, const void* do_, int lddo, const float* lse, const float* delta,
+    int N, int heads, float scale_log2, float scale, bf16_t* dqkv, int lddqkv, int nblk,
+    float* rinv, DropKey dk) {      // (the kernels' own arguments carry the __restrict__)
   using C = BwdCfg<DKP, X3>;
   using T = std::conditional_t<X3, float, bf16_t>;
   typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
@@ -313,11 +317,25 @@ __global__ __launch_bounds__(64 * bwd_waves(DKP, X3), bwd_min_blocks(DKP, X3)) v
           ir4[g] = f32x4{ir, ir, ir, ir};
         }
       }
+      // DROP: the tile's 16 keep bits per lane first, while the score registers are not yet
+      // live (bit 4 g + j: streamed row t0 + 8 g + 4 half + j, stationary row s0 + col)
+      uint32_t keep = 0;
+      if constexpr (DROP) {
+        if (!pre) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int x0 = t0 + 8 * g + 4 * half;
+            keep |= (KV ? drop_keep4_queries(dk, b, h, x0, s0 + col)
+                        : drop_keep4_keys(dk, b, h, s0 + col, x0)) << (4 * g);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
       f32x16 s, dp;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         s[r] = X3 ? 0.f : nl4[r >> 2][r & 3];
-        dp[r] = nd4[r >> 2][r & 3];
+        dp[r] = DROP ? 0.f : nd4[r >> 2][r & 3];
       }
       const char* r1 = img1 + col * C::VS + half * 16;
       const char* r2 = img2 + col * C::VS + half * 16;
@@ -368,8 +386,20 @@ __global__ __launch_bounds__(64 * bwd_waves(DKP, X3), bwd_min_blocks(DKP, X3)) v
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] *= ir4[r >> 2][r & 3];
       }
+      if constexpr (DROP) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const bool k = (keep >> (4 * g + j)) & 1u;
+            dp[4 * g + j] = ((k ? dp[4 * g + j] * dk.inv_keep : 0.f) + nd4[g][j]) * s[4 * g + j];
+            if constexpr (KV) s[4 * g + j] = k ? s[4 * g + j] * dk.inv_keep : 0.f;   // dV's operand
+          }
+        }
+      } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) dp[r] *= s[r];
+      }
 #pragma unroll
       for (int st = 0; st < 2; ++st) {
         const f32x4 p0 = {s[8 * st + 0], s[8 * st + 1], s[8 * st + 2], s[8 * st + 3]};
@@ -451,12 +481,51 @@ __global__ __launch_bounds__(64 * bwd_waves(DKP, X3), bwd_min_blocks(DKP, X3)) v
 }
 
 template <int DKP, bool X3, bool KV>
+__global__ __launch_bounds__(64 * bwd_waves(DKP, X3), bwd_min_blocks(DKP, X3)) void attn_bwd_kernel(
+    const void* __restrict__ qkv_, int ldqkv, const void* __restrict__ do_, int lddo,
+    const float* __restrict__ lse, const float* __restrict__ delta, int N, int heads,
+    float scale_log2, float scale, bf16_t* __restrict__ dqkv, int lddqkv, int nblk,
+    float* __restrict__ rinv) {
+  attn_bwd_body<DKP, X3, KV, false>(qkv_, ldqkv, do_, lddo, lse, delta, N, heads, scale_log2, scale,
+                                    dqkv, lddqkv, nblk, rinv, DropKey{});
+}
+// launch bounds of its own: one workgroup fewer per CU where the mask arithmetic needs the
+// registers (DESIGN.md "Dropout", resource table)
+constexpr int bwd_drop_min_blocks(int dkp, bool x3) {
+  return dkp == 128 || x3 ? 1 : (dkp == 64 ? 2 : 3);
+}
+template <int DKP, bool X3, bool KV>
+__global__ __launch_bounds__(64 * bwd_waves(DKP, X3), bwd_drop_min_blocks(DKP, X3))
+void attn_bwd_drop_kernel(
+    const void* __restrict__ qkv_, int ldqkv, const void* __restrict__ do_, int lddo,
+    const float* __restrict__ lse, const float* __restrict__ delta, int N, int heads,
+    float scale_log2, float scale, bf16_t* __restrict__ dqkv, int lddqkv, int nblk,
+    float* __restrict__ rinv, uint32_t dk0, uint32_t dk1, uint32_t dthr, float inv_keep) {
+  const DropKey dk{dk0, dk1, dthr, inv_keep};
+  attn_bwd_body<DKP, X3, KV, true>(qkv_, ldqkv, do_, lddo, lse, delta, N, heads, scale_log2, scale,
+                                   dqkv, lddqkv, nblk, rinv, dk);
+}
+
+template <int DKP, bool X3, bool KV>
 int launch_pass(const void* qkv, int ldqkv, const void* dO, int lddo, const float* lse,
                 float* delta, int B, int N, int heads, float scale, void* dqkv, int lddqkv,
-                hipStream_t stream) {
+                hipStream_t stream, const DropKey* dk) {
   using C = BwdCfg<DKP, X3>;
   static_assert(C::LDS <= 160 * 1024, "LDS budget");
   const int nblk = ((N + 31) / 32 + C::NW - 1) / C::NW;
+  if (dk) {
+    static std::once_flag donce[kMaxDevices];
+    once_per_device(donce, [] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_drop_kernel<DKP, X3, KV>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+    });
+    hipLaunchKernelGGL((attn_bwd_drop_kernel<DKP, X3, KV>), dim3(nblk * heads * B),
+                       dim3(64 * C::NW), C::LDS, stream, qkv, ldqkv, dO, lddo, lse, delta, N, heads,
+                       scale * kLog2e, scale, static_cast<bf16_t*>(dqkv), lddqkv, nblk,
+                       delta + (size_t)B * heads * N, dk->k0, dk->k1, dk->thr, dk->inv_keep);
+    VTD_LAUNCH_CHECK(KV ? "attention_backward_dropout (dK, dV)" : "attention_backward_dropout (dQ)");
+    return VTD_OK;
+  }
   static std::once_flag once[kMaxDevices];
   once_per_device(once, [] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<DKP, X3, KV>),
@@ -473,13 +542,13 @@ int launch_pass(const void* qkv, int ldqkv, const void* dO, int lddo, const floa
 template <int DKP, bool X3>
 int launch_both(const void* qkv, int ldqkv, const void* dO, int lddo, const float* lse,
                 float* delta, int B, int N, int heads, float scale, void* dqkv, int lddqkv,
-                hipStream_t stream) {
+                hipStream_t stream, const DropKey* dk) {
   // the Q pass first: in the split mode it leaves the row sums' reciprocals for the KV pass
   if (int rc = launch_pass<DKP, X3, false>(qkv, ldqkv, dO, lddo, lse, delta, B, N, heads, scale,
-                                           dqkv, lddqkv, stream))
+                                           dqkv, lddqkv, stream, dk))
     return rc;
   return launch_pass<DKP, X3, true>(qkv, ldqkv, dO, lddo, lse, delta, B, N, heads, scale, dqkv,
-                                    lddqkv, stream);
+                                    lddqkv, stream, dk);
 }
 
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
@@ -503,7 +572,7 @@ int attention_backward_workspace_bytes(int B, int N, int heads, int dkp, int dty
 int attention_backward_launch(const void* qkv, const void* o, const void* dO, const float* lse,
                               int B, int N, int heads, int dkp, int ldqkv, int ldo, int lddo,
                               float scale, void* dqkv, int lddqkv, int dtype, void* ws,
-                              size_t ws_bytes, hipStream_t stream) {
+                              size_t ws_bytes, hipStream_t stream, const DropKey* dk) {
   VTD_CHECK_ARG(qkv && o && dO && lse && dqkv && ws, "attention_backward: null pointer");
   VTD_CHECK_ARG(B > 0 && N > 0 && heads > 0, "attention_backward: bad B/N/heads");
   VTD_CHECK_ARG(dkp == 32 || dkp == 64 || dkp == 128, "attention_backward: dkp must be 32/64/128");
@@ -548,7 +617,7 @@ int attention_backward_launch(const void* qkv, const void* o, const void* dO, co
                        B, N, heads, dkp, delta);
   VTD_LAUNCH_CHECK("attention_backward delta");
 #define VTD_BWD(D, X) \
-  launch_both<D, X>(qkv, ldqkv, dO, lddo, lse, delta, B, N, heads, scale, dqkv, lddqkv, stream)
+  launch_both<D, X>(qkv, ldqkv, dO, lddo, lse, delta, B, N, heads, scale, dqkv, lddqkv, stream, dk)
   if (x3) return dkp == 32 ? VTD_BWD(32, true) : dkp == 64 ? VTD_BWD(64, true) : VTD_BWD(128, true);
   return dkp == 32 ? VTD_BWD(32, false) : dkp == 64 ? VTD_BWD(64, false) : VTD_BWD(128, false);
 #undef VTD_BWD
@@ -570,6 +639,19 @@ int vtd_attention_backward(const void* qkv_dev, const void* o_dev, const void* d
   return vtd::attention_backward_launch(qkv_dev, o_dev, do_dev, lse_dev, B, N, heads, dkp, ldqkv,
                                         ldo, lddo, scale, dqkv_dev, lddqkv, dtype, ws_dev, ws_bytes,
                                         static_cast<hipStream_t>(stream));
+}
+
+int vtd_attention_backward_dropout(const void* qkv_dev, const void* o_dev, const void* do_dev,
+                                   const float* lse_dev, int B, int N, int heads, int dkp,
+                                   int ldqkv, int ldo, int lddo, float scale, void* dqkv_dev,
+                                   int lddqkv, int dtype, void* ws_dev, size_t ws_bytes,
+                                   void* stream, const vtd_dropout* drop) {
+  vtd::DropKey dk;
+  bool on;
+  if (int rc = vtd::drop_prepare("vtd_attention_backward_dropout", drop, &dk, &on)) return rc;
+  return vtd::attention_backward_launch(qkv_dev, o_dev, do_dev, lse_dev, B, N, heads, dkp, ldqkv,
+                                        ldo, lddo, scale, dqkv_dev, lddqkv, dtype, ws_dev, ws_bytes,
+                                        static_cast<hipStream_t>(stream), on ? &dk : nullptr);
 }
 
 }  // extern "C"

@@ -143,6 +143,28 @@ __global__ __launch_bounds__(256) void block_resid_act_kernel(const float* __res
   }
 }
 
+// y = x1 + drop(act(z)): the reference drops after the last MLP layer too, before the residual
+// add.  One thread per 4 columns (one Philox block, vtd_philox.h); one fp32 multiply by inv_keep.
+__global__ __launch_bounds__(256) void block_resid_act_drop_kernel(
+    const float* __restrict__ x1, int ldx, const float* __restrict__ z, int ldz, int64_t rows,
+    int D, int act, float* __restrict__ y, int ldy, DropKey dk) {
+  const int chunks = (D + 3) / 4;
+  const int64_t total = rows * chunks;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = i / chunks;
+    const int cb = (int)(i - m * chunks);
+    const uint32_t keep = drop_keep4_rows(dk, m, (uint32_t)cb);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int c = cb * 4 + j;
+      if (c < D)
+        y[m * ldy + c] = x1[m * ldx + c] +
+                         ((keep >> j) & 1u ? apply_act(act, z[m * ldz + c]) * dk.inv_keep : 0.f);
+    }
+  }
+}
+
 int grid_of(int64_t total) { return (int)std::min<int64_t>((total + 255) / 256, 16384); }
 
 int gather_check(const char* what, const BlockGather& g) {
@@ -216,10 +238,17 @@ int block_ungather_launch(const BlockGather& g, float* const* dst, float* const*
 }
 
 int block_resid_act_launch(const float* x1, int ldx, const float* z, int ldz, int64_t rows, int D,
-                           int act, float* y, int ldy, hipStream_t st) {
+                           int act, float* y, int ldy, hipStream_t st, const DropKey* dk) {
   VTD_CHECK_ARG(x1 && z && y && rows > 0 && D > 0 && ldx >= D && ldz >= D && ldy >= D,
                 "block_resid_act: bad arguments");
   VTD_CHECK_ARG(act >= VTD_ACT_NONE && act <= VTD_ACT_MISH, "block_resid_act: unknown activation");
+  if (dk) {
+    ProfScope ps(st, PROF_OTHER, 0.0);
+    hipLaunchKernelGGL(block_resid_act_drop_kernel, dim3(grid_of(rows * ((D + 3) / 4))), dim3(256),
+                       0, st, x1, ldx, z, ldz, rows, D, act, y, ldy, *dk);
+    VTD_LAUNCH_CHECK("block_resid_act (dropout)");
+    return VTD_OK;
+  }
   auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
   const bool vec = D % 4 == 0 && ldx % 4 == 0 && ldz % 4 == 0 && ldy % 4 == 0 && al16(x1) &&
                    al16(z) && al16(y);

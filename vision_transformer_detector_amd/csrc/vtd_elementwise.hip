@@ -1071,18 +1071,26 @@ __device__ __forceinline__ void store_op8(const float (&v)[8], bf16_t* yr, int c
 
 // MODE 0: y = act(z); MODE 1: y = ga * act'(z).  One thread per 8 columns of a row of the
 // P-wide output piece; columns [N, P) zero.
-template <int MODE>
-__global__ __launch_bounds__(256) void act_op_kernel(const float* __restrict__ z, int ldz,
-                                                     const float* __restrict__ ga, int ldga,
-                                                     int64_t rows, int N, int act,
-                                                     bf16_t* __restrict__ y, int ldy, int P,
-                                                     int x3) {
+// DROP: the value (MODE 0) or the incoming gradient (MODE 1) passes the dropout mask of
+// (row m, column c) first: kept values times inv_keep -- one fp32 multiply before the single
+// rounding into the stored form -- dropped ones +0 (vtd_philox.h).
+template <int MODE, bool DROP>
+__device__ __forceinline__ void act_op_body(const float* __restrict__ z, int ldz,
+                                            const float* __restrict__ ga, int ldga,
+                                            int64_t rows, int N, int act,
+                                            bf16_t* __restrict__ y, int ldy, int P, int x3,
+                                            DropKey dk) {
   const int chunks = P / 8;
   const int64_t total = rows * chunks;
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
        g += (int64_t)gridDim.x * blockDim.x) {
     const int64_t m = g / chunks;
     const int c0 = (int)(g - m * chunks) * 8;
+    uint32_t keep = 0;
+    if constexpr (DROP) {
+      if (c0 < N) keep = drop_keep4_rows(dk, m, (uint32_t)c0 >> 2);
+      if (c0 + 4 < N) keep |= drop_keep4_rows(dk, m, ((uint32_t)c0 >> 2) + 1) << 4;
+    }
     float v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -1092,15 +1100,91 @@ __global__ __launch_bounds__(256) void act_op_kernel(const float* __restrict__ z
         const float x = z[m * ldz + c];
         if (MODE == 0) {
           r = apply_act(act, x);
+          if constexpr (DROP) r = (keep >> i) & 1u ? r * dk.inv_keep : 0.f;
         } else {
           const float d = act == VTD_ACT_MISH ? act_mish_grad(x)
                           : act == VTD_ACT_GELU_TANH ? act_gelu_grad(x) : 1.f;
-          r = ga[m * ldga + c] * d;
+          const float g = ga[m * ldga + c];
+          if constexpr (DROP) r = (keep >> i) & 1u ? (g * dk.inv_keep) * d : 0.f;   // dropped: +0
+          else r = g * d;
         }
       }
       v[i] = r;
     }
     store_op8(v, y + m * ldy, c0, P, x3 != 0);
+  }
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void act_op_kernel(const float* __restrict__ z, int ldz,
+                                                     const float* __restrict__ ga, int ldga,
+                                                     int64_t rows, int N, int act,
+                                                     bf16_t* __restrict__ y, int ldy, int P,
+                                                     int x3) {
+  act_op_body<MODE, false>(z, ldz, ga, ldga, rows, N, act, y, ldy, P, x3, DropKey{});
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void act_op_drop_kernel(const float* __restrict__ z, int ldz,
+                                                          const float* __restrict__ ga, int ldga,
+                                                          int64_t rows, int N, int act,
+                                                          bf16_t* __restrict__ y, int ldy, int P,
+                                                          int x3, DropKey dk) {
+  act_op_body<MODE, true>(z, ldz, ga, ldga, rows, N, act, y, ldy, P, x3, dk);
+}
+
+// y = drop(x), fp32 [rows][N] -> fp32 [rows][N] (the Keras Dropout layer on its own; its
+// gradient is the same map applied to the incoming gradient).  One thread per 4 columns.
+__global__ __launch_bounds__(256) void dropout_f32_kernel(const float* __restrict__ x, int ldx,
+                                                          int64_t rows, int N,
+                                                          float* __restrict__ y, int ldy,
+                                                          DropKey dk) {
+  const int chunks = (N + 3) / 4;
+  const int64_t total = rows * chunks;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = g / chunks;
+    const int cb = (int)(g - m * chunks);
+    const uint32_t keep = drop_keep4_rows(dk, m, (uint32_t)cb);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = cb * 4 + i;
+      if (c < N) y[m * ldy + c] = (keep >> i) & 1u ? x[m * ldx + c] * dk.inv_keep : 0.f;
+    }
+  }
+}
+
+// the mask itself, one byte per element (1 = kept): out [rows][ldo], columns < N written
+__global__ __launch_bounds__(256) void dropout_mask_kernel(int64_t rows, int N,
+                                                           uint8_t* __restrict__ out, int ldo,
+                                                           DropKey dk) {
+  const int chunks = (N + 3) / 4;
+  const int64_t total = rows * chunks;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t m = g / chunks;
+    const int cb = (int)(g - m * chunks);
+    const uint32_t keep = drop_keep4_rows(dk, m, (uint32_t)cb);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (cb * 4 + i < N) out[m * ldo + cb * 4 + i] = (uint8_t)((keep >> i) & 1u);
+  }
+}
+// attention site: out [B][heads][N][N], through the kernels' own function (4 keys of a query)
+__global__ __launch_bounds__(256) void dropout_mask_attention_kernel(int B, int heads, int N,
+                                                                     uint8_t* __restrict__ out,
+                                                                     DropKey dk) {
+  const int chunks = (N + 3) / 4;
+  const int64_t total = (int64_t)B * heads * N * chunks;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
+       g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = g / chunks;               // (b heads + h) N + i
+    const int cb = (int)(g - r * chunks);
+    const int i = (int)(r % N);
+    const int64_t bh = r / N;
+    const int h = (int)(bh % heads), b = (int)(bh / heads);
+    const uint32_t keep = drop_keep4_keys(dk, b, h, i, cb * 4);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (cb * 4 + c < N) out[r * N + cb * 4 + c] = (uint8_t)((keep >> c) & 1u);
   }
 }
 
@@ -1247,6 +1331,45 @@ int act_grad_launch(const float* z, int ldz, const float* ga, int ldga, int64_t 
   return VTD_OK;
 }
 
+int drop_prepare(const char* what, const vtd_dropout* d, DropKey* key, bool* on) {
+  const std::string w(what);
+  VTD_CHECK_ARG(d, w + ": null dropout description");
+  VTD_CHECK_ARG(d->rate >= 0.f && d->rate < 1.f, w + ": dropout rate must be in [0, 1)");   // NaN fails
+  *on = d->rate > 0.f;
+  *key = drop_key(d->seed, d->step, d->site, d->rate);
+  return VTD_OK;
+}
+
+int act_forward_drop_launch(const float* z, int64_t rows, int N, int ldz, int act, void* y, int ldy,
+                            int dtype, const DropKey& dk, hipStream_t st) {
+  VTD_CHECK_ARG(z && y && rows > 0 && N > 0 && ldz >= N, "act_forward_dropout: bad arguments");
+  VTD_CHECK_ARG(act >= VTD_ACT_NONE && act <= VTD_ACT_MISH,
+                "act_forward_dropout: unknown activation");
+  int P;
+  if (int rc = op_form("act_forward_dropout", y, ldy, dtype, N, &P)) return rc;
+  ProfScope ps(st, PROF_OTHER, 0.0);
+  hipLaunchKernelGGL(act_op_drop_kernel<0>, dim3(op_grid(rows * (P / 8))), dim3(256), 0, st, z, ldz,
+                     (const float*)nullptr, 0, rows, N, act, static_cast<bf16_t*>(y), ldy, P,
+                     dtype == VTD_BF16X3 ? 1 : 0, dk);
+  VTD_LAUNCH_CHECK("act_forward_dropout");
+  return VTD_OK;
+}
+
+int act_grad_drop_launch(const float* z, int ldz, const float* ga, int ldga, int64_t rows, int N,
+                         int act, void* y, int ldy, int dtype, const DropKey& dk, hipStream_t st) {
+  VTD_CHECK_ARG(z && ga && y && rows > 0 && N > 0 && ldz >= N && ldga >= N,
+                "act_grad_dropout: bad arguments");
+  VTD_CHECK_ARG(act >= VTD_ACT_NONE && act <= VTD_ACT_MISH, "act_grad_dropout: unknown activation");
+  int P;
+  if (int rc = op_form("act_grad_dropout", y, ldy, dtype, N, &P)) return rc;
+  ProfScope ps(st, PROF_OTHER, 0.0);
+  hipLaunchKernelGGL(act_op_drop_kernel<1>, dim3(op_grid(rows * (P / 8))), dim3(256), 0, st, z, ldz,
+                     ga, ldga, rows, N, act, static_cast<bf16_t*>(y), ldy, P,
+                     dtype == VTD_BF16X3 ? 1 : 0, dk);
+  VTD_LAUNCH_CHECK("act_grad_dropout");
+  return VTD_OK;
+}
+
 int head_unscatter_launch(const float* dU, int B, int T, int ldu, void* y, int ldy, int dtype,
                           hipStream_t st) {
   VTD_CHECK_ARG(dU && y && B > 0 && T > 0 && ldu >= T, "head_unscatter: bad arguments");
@@ -1274,6 +1397,73 @@ int vtd_act_grad(const float* z_dev, int ldz, const float* ga_dev, int ldga, int
                  int act, void* gz_dev, int ldgz, int dtype, void* stream) {
   return vtd::act_grad_launch(z_dev, ldz, ga_dev, ldga, rows, N, act, gz_dev, ldgz, dtype,
                               static_cast<hipStream_t>(stream));
+}
+
+int vtd_act_forward_dropout(const float* z_dev, int64_t rows, int N, int ldz, int act, void* a_dev,
+                            int lda, int dtype, void* stream, const vtd_dropout* drop) {
+  vtd::DropKey dk;
+  bool on;
+  if (int rc = vtd::drop_prepare("vtd_act_forward_dropout", drop, &dk, &on)) return rc;
+  if (!on) return vtd_act_forward(z_dev, rows, N, ldz, act, a_dev, lda, dtype, stream);
+  return vtd::act_forward_drop_launch(z_dev, rows, N, ldz, act, a_dev, lda, dtype, dk,
+                                      static_cast<hipStream_t>(stream));
+}
+
+int vtd_act_grad_dropout(const float* z_dev, int ldz, const float* ga_dev, int ldga, int64_t rows,
+                         int N, int act, void* gz_dev, int ldgz, int dtype, void* stream,
+                         const vtd_dropout* drop) {
+  vtd::DropKey dk;
+  bool on;
+  if (int rc = vtd::drop_prepare("vtd_act_grad_dropout", drop, &dk, &on)) return rc;
+  if (!on)
+    return vtd_act_grad(z_dev, ldz, ga_dev, ldga, rows, N, act, gz_dev, ldgz, dtype, stream);
+  return vtd::act_grad_drop_launch(z_dev, ldz, ga_dev, ldga, rows, N, act, gz_dev, ldgz, dtype, dk,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int vtd_dropout_apply(const vtd_dropout* drop, const float* x_dev, int ldx, int64_t rows, int N,
+                      float* y_dev, int ldy, void* stream) {
+  using namespace vtd;
+  DropKey dk;
+  bool on;
+  if (int rc = drop_prepare("vtd_dropout_apply", drop, &dk, &on)) return rc;
+  VTD_CHECK_ARG(x_dev && y_dev && rows > 0 && N > 0 && ldx >= N && ldy >= N,
+                "vtd_dropout_apply: bad arguments");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  ProfScope ps(st, PROF_OTHER, 0.0);
+  hipLaunchKernelGGL(dropout_f32_kernel, dim3(op_grid(rows * ((N + 3) / 4))), dim3(256), 0, st,
+                     x_dev, ldx, rows, N, y_dev, ldy, dk);
+  VTD_LAUNCH_CHECK("vtd_dropout_apply");
+  return VTD_OK;
+}
+
+int vtd_dropout_mask(const vtd_dropout* drop, int64_t rows, int N, uint8_t* out_dev, int ldo,
+                     void* stream) {
+  using namespace vtd;
+  DropKey dk;
+  bool on;
+  if (int rc = drop_prepare("vtd_dropout_mask", drop, &dk, &on)) return rc;
+  VTD_CHECK_ARG(out_dev && rows > 0 && N > 0 && ldo >= N, "vtd_dropout_mask: bad arguments");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3(op_grid(rows * ((N + 3) / 4))), dim3(256), 0, st,
+                     rows, N, out_dev, ldo, dk);
+  VTD_LAUNCH_CHECK("vtd_dropout_mask");
+  return VTD_OK;
+}
+
+int vtd_dropout_mask_attention(const vtd_dropout* drop, int B, int heads, int N, uint8_t* out_dev,
+                               void* stream) {
+  using namespace vtd;
+  DropKey dk;
+  bool on;
+  if (int rc = drop_prepare("vtd_dropout_mask_attention", drop, &dk, &on)) return rc;
+  VTD_CHECK_ARG(out_dev && B > 0 && heads > 0 && N > 0, "vtd_dropout_mask_attention: bad arguments");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(dropout_mask_attention_kernel,
+                     dim3(op_grid((int64_t)B * heads * N * ((N + 3) / 4))), dim3(256), 0, st, B,
+                     heads, N, out_dev, dk);
+  VTD_LAUNCH_CHECK("vtd_dropout_mask_attention");
+  return VTD_OK;
 }
 
 int vtd_head_unscatter(const float* dU_dev, int B, int T, int ldu, void* dT_dev, int ldt,

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "vtd_common.h"
+#include "vtd_philox.h"
 
 namespace vtd {
 
@@ -45,6 +46,10 @@ int attention_mx8_launch(const void* qkv, int B, int N, int heads, int dkp, int 
 int attention_train_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
                            float scale, void* out, int ldo, float* lse, int dtype,
                            hipStream_t stream);
+// the same with dropout on the attention probabilities (DROP instantiations; dk from drop_prepare)
+int attention_train_drop_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
+                                float scale, void* out, int ldo, float* lse, int dtype,
+                                const DropKey& dk, hipStream_t stream);
 
 // ----------------------------------------------------------------- vtd_attention_bwd.hip
 int attention_backward_workspace_bytes(int B, int N, int heads, int dkp, int dtype,
@@ -52,9 +57,15 @@ int attention_backward_workspace_bytes(int B, int N, int heads, int dkp, int dty
 int attention_backward_launch(const void* qkv, const void* o, const void* dO, const float* lse,
                               int B, int N, int heads, int dkp, int ldqkv, int ldo, int lddo,
                               float scale, void* dqkv, int lddqkv, int dtype, void* ws,
-                              size_t ws_bytes, hipStream_t stream);
+                              size_t ws_bytes, hipStream_t stream, const DropKey* dk = nullptr);
 
 // ----------------------------------------------------------------- vtd_elementwise.hip
+// checks a vtd_dropout (non-null, rate in [0, 1)) and derives what the kernels take; *on = rate > 0
+int drop_prepare(const char* what, const vtd_dropout* d, DropKey* key, bool* on);
+int act_forward_drop_launch(const float* z, int64_t rows, int N, int ldz, int act, void* y, int ldy,
+                            int dtype, const DropKey& dk, hipStream_t st);
+int act_grad_drop_launch(const float* z, int ldz, const float* ga, int ldga, int64_t rows, int N,
+                         int act, void* y, int ldy, int dtype, const DropKey& dk, hipStream_t st);
 int layernorm_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx, const float* g,
                      const float* b, float eps, void* y, int ldy, int dtype, hipStream_t st);
 int layernorm_mx8_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx,
@@ -108,9 +119,9 @@ int block_gather_bias_launch(const BlockGather& g, float* dst, hipStream_t st);
 // (dstb[part] [N]); g.src is not read
 int block_ungather_launch(const BlockGather& g, float* const* dst, float* const* dstb,
                           const float* W, int ldw, const float* b, hipStream_t st);
-// y = x1 + act(z), fp32 [rows][D]
+// y = x1 + act(z), fp32 [rows][D]; dk: y = x1 + drop(act(z))
 int block_resid_act_launch(const float* x1, int ldx, const float* z, int ldz, int64_t rows, int D,
-                           int act, float* y, int ldy, hipStream_t st);
+                           int act, float* y, int ldy, hipStream_t st, const DropKey* dk = nullptr);
 
 // ----------------------------------------------------------------- vtd_mx8.hip
 int quantize_mx8_launch(const void* x, int x_dtype, int64_t rows, int K, int ldx, int Kq,

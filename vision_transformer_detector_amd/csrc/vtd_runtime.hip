@@ -1213,9 +1213,23 @@ int block_plan(const BlockShape& s, const Mode& m, int dtype, BlockPlan* out) {
 static int encoder_block_backward(const vtd_block_dims* c, const vtd_block_params* w,
                                   const float* x, const float* dy, float* y,
                                   const vtd_block_grads* g, void* ws_, size_t ws_bytes,
-                                  void* stream_) {
+                                  void* stream_, const vtd_block_dropout* drop = nullptr) {
   BlockShape s;
   if (int rc = block_shape(c, &s, "encoder_block_backward")) return rc;
+  // dropout (optional): site_base the attention probabilities, site_base + 1 + j MLP layer j.
+  // The backward's recomputed forward regenerates the forward's masks: the same (seed, step, site)
+  DropKey dk_att{}, dk_mlp[VTD_MAX_MLP]{};
+  bool drop_on = false;
+  if (drop) {
+    VTD_CHECK_ARG((uint64_t)drop->site_base + s.q <= 0xffffffffull,
+                  "encoder_block_backward_dropout: site_base + mlp_quantities overflows 32 bits");
+    for (int j = -1; j < s.q; ++j) {
+      const vtd_dropout d{drop->seed, drop->step, drop->site_base + (uint32_t)(1 + j), drop->rate};
+      if (int rc = drop_prepare("encoder_block_backward_dropout", &d, j < 0 ? &dk_att : &dk_mlp[j],
+                                &drop_on))
+        return rc;
+    }
+  }
   VTD_CHECK_ARG(w && x && ws_ && (dy ? g != nullptr : y != nullptr),
                 "encoder_block_backward: null pointer");
   VTD_CHECK_ARG(w->ln1_gamma && w->ln1_beta && w->wq && w->bq && w->wk && w->bk && w->wv && w->bv &&
@@ -1294,8 +1308,10 @@ static int encoder_block_backward(const vtd_block_dims* c, const vtd_block_param
     if ((rc = gemm(s.qkv_p, m.kk(Dp), h1, m.ka(Dp), wt, P.f_qkv, e, 2.0 * R * D * 3.0 * s.inner)))
       return rc;
   }
-  if ((rc = attention_train_launch(qkv, s.B, s.T, s.H, s.dkp, s.qkv_p, scale, attn,
-                                   m.ka(s.inner_p), lse, c->dtype, st)))
+  if ((rc = drop_on ? attention_train_drop_launch(qkv, s.B, s.T, s.H, s.dkp, s.qkv_p, scale, attn,
+                                                  m.ka(s.inner_p), lse, c->dtype, dk_att, st)
+                    : attention_train_launch(qkv, s.B, s.T, s.H, s.dkp, s.qkv_p, scale, attn,
+                                             m.ka(s.inner_p), lse, c->dtype, st)))
     return rc;
   {                                   // x1 = x + O Wo + bo
     if ((rc = block_gather_launch(go, wt, nullptr, op, st))) return rc;
@@ -1322,13 +1338,17 @@ static int encoder_block_backward(const vtd_block_dims* c, const vtd_block_param
       e.out = ws + P.z[j]; e.ldo = up; e.out_dtype = VTD_F32;
       if ((rc = gemm(up, m.kk(k), a, m.ka(k), wt, P.f_mlp[j], e, 2.0 * R * kv * uv))) return rc;
       if (j + 1 < q) {
-        if ((rc = act_forward_launch(f32p(P.z[j]), R, uv, up, act, ws + P.a[j], m.ka(up), op, st)))
+        if ((rc = drop_on ? act_forward_drop_launch(f32p(P.z[j]), R, uv, up, act, ws + P.a[j],
+                                                    m.ka(up), op, dk_mlp[j], st)
+                          : act_forward_launch(f32p(P.z[j]), R, uv, up, act, ws + P.a[j], m.ka(up),
+                                               op, st)))
           return rc;
         a = ws + P.a[j];
       }
     }
   }
-  if (y && (rc = block_resid_act_launch(x1, D, f32p(P.z[q - 1]), s.up[q - 1], R, D, act, y, D, st)))
+  if (y && (rc = block_resid_act_launch(x1, D, f32p(P.z[q - 1]), s.up[q - 1], R, D, act, y, D, st,
+                                        drop_on ? &dk_mlp[q - 1] : nullptr)))
     return rc;
 
   if (!dy) return VTD_OK;              // the training forward alone (y_dev)
@@ -1342,7 +1362,10 @@ static int encoder_block_backward(const vtd_block_dims* c, const vtd_block_param
     const int up = s.up[j], uv = s.u[j];
     const int kin = j ? s.up[j - 1] : Dp, kinv = j ? s.u[j - 1] : D;
     const void* ain = j ? ws + P.a[j - 1] : h2;
-    if ((rc = act_grad_launch(f32p(P.z[j]), up, gin, ldgin, R, uv, act, gz, m.ka(up), op, st)))
+    if ((rc = drop_on ? act_grad_drop_launch(f32p(P.z[j]), up, gin, ldgin, R, uv, act, gz, m.ka(up),
+                                             op, dk_mlp[j], st)
+                      : act_grad_launch(f32p(P.z[j]), up, gin, ldgin, R, uv, act, gz, m.ka(up), op,
+                                        st)))
       return rc;
     if ((rc = wgrad(kinv, uv, ain, m.ka(kin), gz, m.ka(up), g->w_mlp[j], uv, g->b_mlp[j],
                     P.wg_mlp[j])))
@@ -1383,7 +1406,8 @@ static int encoder_block_backward(const vtd_block_dims* c, const vtd_block_param
   void* dqkv = ws + P.dqkv;
   if ((rc = attention_backward_launch(qkv, attn, dO, lse, s.B, s.T, s.H, s.dkp, s.qkv_p,
                                       m.ka(s.inner_p), s.inner_p, scale, dqkv, m.ka(s.qkv_p),
-                                      c->dtype, ws + P.att, P.att_bytes, st)))
+                                      c->dtype, ws + P.att, P.att_bytes, st,
+                                      drop_on ? &dk_att : nullptr)))
     return rc;
   // 5. query / key / value
   if ((rc = wgrad(D, s.qkv_p, h1, m.ka(Dp), dqkv, m.ka(s.qkv_p), f32p(P.dwqkv), s.qkv_p,
@@ -1426,6 +1450,17 @@ int vtd_encoder_block_backward(const vtd_block_dims* dims, const vtd_block_param
                                const vtd_block_grads* grads, void* ws, size_t ws_bytes,
                                void* stream) {
   return encoder_block_backward(dims, params, x_dev, dy_dev, y_dev, grads, ws, ws_bytes, stream);
+}
+
+int vtd_encoder_block_backward_dropout(const vtd_block_dims* dims, const vtd_block_params* params,
+                                       const float* x_dev, const float* dy_dev, float* y_dev,
+                                       const vtd_block_grads* grads, void* ws, size_t ws_bytes,
+                                       void* stream, const vtd_block_dropout* drop) {
+  VTD_CHECK_ARG(drop, "encoder_block_backward_dropout: null dropout description");
+  VTD_CHECK_ARG(drop->rate >= 0.f && drop->rate < 1.f,
+                "encoder_block_backward_dropout: dropout rate must be in [0, 1)");
+  return encoder_block_backward(dims, params, x_dev, dy_dev, y_dev, grads, ws, ws_bytes, stream,
+                                drop);
 }
 
 }  // extern "C"

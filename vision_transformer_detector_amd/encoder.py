@@ -1,8 +1,10 @@
 """One encoder block of the detector as a differentiable op on device tensors.
 
-encoder_block(x, weights, ...) is the reference's block with dropout=None (vtd.py:350-412):
+encoder_block(x, weights, ...) is the reference's block (vtd.py:350-412):
 x1 = x + MultiHeadAttention(LayerNorm(x)), y = x1 + MLP(LayerNorm(x1)), from the block's Keras
-weights in their Keras shapes.  Forward and backward are one vtd_encoder_block_backward call
+weights in their Keras shapes; with `dropout` the MultiHeadAttention dropout on the attention
+probabilities and a Dropout after every MLP activation, masks generated inside the kernels from
+(seed, step, site_base).  Forward and backward are one vtd_encoder_block_backward call
 each (include/vtd.h): the forward keeps only x and the weights, the backward recomputes the
 training forward and fills every gradient.  There is no fallback: what the kernels do not cover
 raises.
@@ -70,12 +72,14 @@ def _fill(struct, tensors, q):
     return struct
 
 
-def run(x, weights, dims: L.VtdBlockDims, dy=None, want_dx=True, want_y=True, ws=None, out=None):
+def run(x, weights, dims: L.VtdBlockDims, dy=None, want_dx=True, want_y=True, ws=None, out=None,
+        drop=None):
     """vtd_encoder_block_backward on contiguous fp32 device tensors: x (B, N, d), `weights` the
     block's 12 + 2 q tensors in creation order, dy (B, N, d) or None (the training forward
     alone).  Returns (y or None, grads or None, dx or None): `grads` a list of tensors in the
     weights' order and shapes.  ws: a uint8 workspace of at least workspace_bytes(dims).  out
-    (y, grads, dx): the caller's own output tensors in place of new ones."""
+    (y, grads, dx): the caller's own output tensors in place of new ones.  drop: a
+    VtdBlockDropout (vtd_encoder_block_backward_dropout) or None."""
     q = dims.mlp_quantities
     if ws is None:
         ws = torch.empty(workspace_bytes(dims), device=x.device, dtype=torch.uint8)
@@ -89,11 +93,15 @@ def run(x, weights, dims: L.VtdBlockDims, dy=None, want_dx=True, want_y=True, ws
         if want_dx:
             dx = odx if odx is not None else torch.empty_like(x)
             gstruct.dx = dx.data_ptr()
-    with torch.cuda.device(x.device):
-        L.check(L.lib.vtd_encoder_block_backward(
-            ctypes.byref(dims), ctypes.byref(params), x.data_ptr(), L.ptr(dy), L.ptr(y),
+    args = (ctypes.byref(dims), ctypes.byref(params), x.data_ptr(), L.ptr(dy), L.ptr(y),
             ctypes.byref(gstruct) if gstruct is not None else None, ws.data_ptr(), ws.numel(),
-            L.stream_ptr()), "vtd_encoder_block_backward")
+            L.stream_ptr())
+    with torch.cuda.device(x.device):
+        if drop is None:
+            L.check(L.lib.vtd_encoder_block_backward(*args), "vtd_encoder_block_backward")
+        else:
+            L.check(L.lib.vtd_encoder_block_backward_dropout(*args, ctypes.byref(drop)),
+                    "vtd_encoder_block_backward_dropout")
     return y, grads, dx
 
 
@@ -103,10 +111,12 @@ class _EncoderBlock(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, dims, *weights):
+        dims, drop = dims if isinstance(dims, tuple) else (dims, None)
         xd = x.detach()
         wd = [t.detach().contiguous() for t in weights]
-        y, _, _ = run(xd, wd, dims)
+        y, _, _ = run(xd, wd, dims, drop=drop)
         ctx.dims = dims
+        ctx.drop = drop
         ctx.save_for_backward(xd, *wd)
         return y
 
@@ -116,12 +126,13 @@ class _EncoderBlock(torch.autograd.Function):
         xd, *wd = ctx.saved_tensors
         dy = gy.to(torch.float32).reshape(xd.shape).contiguous()
         need = ctx.needs_input_grad
-        _, grads, dx = run(xd, wd, ctx.dims, dy=dy, want_dx=need[0], want_y=False)
+        _, grads, dx = run(xd, wd, ctx.dims, dy=dy, want_dx=need[0], want_y=False, drop=ctx.drop)
         return (dx, None) + tuple(g if n else None for g, n in zip(grads, need[2:]))
 
 
-def encoder_block(x, weights, *, num_heads, key_dim, use_mish=True, dtype="bf16x3"):
-    """One encoder block (vtd.py:350-412, dropout=None), differentiable w.r.t. x and every weight.
+def encoder_block(x, weights, *, num_heads, key_dim, use_mish=True, dtype="bf16x3", dropout=None,
+                  seed=None, step=0, site_base=0):
+    """One encoder block (vtd.py:350-412), differentiable w.r.t. x and every weight.
 
     x: float32 device tensor (B, N, d).  weights: a sequence (or an OrderedDict, whose values are
     taken) of float32 device tensors in the Keras creation order of one block, in Keras shapes:
@@ -132,7 +143,15 @@ def encoder_block(x, weights, *, num_heads, key_dim, use_mish=True, dtype="bf16x
     'bf16x3' or 'bfloat16', the operand mode of the Dense products and the attention core; the
     residual stream and every gradient are float32.  Returns y (B, N, d); backward() makes one
     vtd_encoder_block_backward call, bit-identical from run to run, with no synchronisation;
-    inputs that do not require grad get None."""
+    inputs that do not require grad get None.
+
+    dropout: the reference's `dropout` rate inside the block, training semantics: on the
+    attention probabilities (site `site_base`) and after the activation of MLP layer j (site
+    `site_base + 1 + j`; the last layer's too, before the residual add).  None or 0 is the block
+    without dropout, bit for bit.  A positive rate needs `seed`: every mask bit is a function of
+    (seed, step, site, index) alone, and the backward regenerates the forward's masks.  Blocks
+    chained through autograd must take distinct site_base values: i * (1 + mlp_quantities) for
+    block i; advance `step` once per training step."""
     if isinstance(weights, dict):
         weights = list(weights.values())
     else:
@@ -167,4 +186,11 @@ def encoder_block(x, weights, *, num_heads, key_dim, use_mish=True, dtype="bf16x
         if tuple(t.shape) != tuple(shape):
             raise ValueError(f"encoder_block: {what} has shape {tuple(t.shape)}, expected {shape}")
     dims = block_dims(B, N, d, num_heads, key_dim, q, use_mish, dtype)
-    return _EncoderBlock.apply(x.contiguous(), dims, *weights)
+    from .dropout import spec
+    d1 = spec("encoder_block", dropout, seed, step, site_base)
+    if d1 is None:
+        return _EncoderBlock.apply(x.contiguous(), dims, *weights)
+    if int(site_base) + q >= 1 << 32:
+        raise ValueError("encoder_block: site_base + mlp_quantities must fit 32 bits")
+    drop = L.VtdBlockDropout(seed=d1.seed, step=d1.step, site_base=d1.site, rate=d1.rate)
+    return _EncoderBlock.apply(x.contiguous(), (dims, drop), *weights)
