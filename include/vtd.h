@@ -839,6 +839,22 @@ int vtd_encoder_block_backward_dropout(const vtd_block_dims* dims, const vtd_blo
                                        const vtd_block_grads* grads, void* ws, size_t ws_bytes,
                                        void* stream, const vtd_block_dropout* drop);
 
+/* vtd_head_backward with the reference's Dropout after every head Dense + activation
+ * (mlp_head, vtd.py:468-486): drop->site_base + j is the site of head layer j, 0 <= j < n_head
+ * (vtd_dims.n_head, repeats included).  None follows Dense(17) or MLP_Head_no_Sigmoid.  The site
+ * is an elementwise one over the unpadded [batch * 17][head_units[j]] activation, row b * 17 + r:
+ * vtd_dropout_mask(rows = batch * 17, N = head_units[j]); head_units_p and leading dimensions
+ * never enter.  The forward-only call (dlogits_dev NULL) and the forward + backward call
+ * regenerate the same masks from the same (seed, step, site_base).  Same workspace
+ * (vtd_head_backward_workspace_bytes), same checks; in addition VTD_ERR_INVALID_ARG before any
+ * device call for a NULL drop, a rate outside [0, 1) (NaN included) or site_base + n_head beyond
+ * 32 bits.  rate == 0: vtd_head_backward's launches and bits.  In one model the head's site_base
+ * is repeat_times * (1 + mlp_quantities), after the blocks' sites. */
+int vtd_head_backward_dropout(const vtd_config* cfg, const vtd_head_params* w,
+                              const float* encoded_dev, const float* dlogits_dev,
+                              float* logits_dev, const vtd_head_grads* g, void* ws,
+                              size_t ws_bytes, void* stream, const vtd_block_dropout* drop);
+
 /* ---- patch embedding backward (additions to ABI 17; DESIGN.md "Whole-model gradients")
  * The stem of the reference (transformer_preprocessor, vtd.py:271-307):
  *   x0[b N + n][j] = sum_k patches[b N + n][k] W[k][j] + bias[j] + pos[n],

@@ -124,7 +124,8 @@ class VtdDropout(ctypes.Structure):
 
 
 class VtdBlockDropout(ctypes.Structure):
-    """vtd_block_dropout: site_base the attention probabilities, site_base + 1 + j MLP layer j."""
+    """vtd_block_dropout: site_base the attention probabilities, site_base + 1 + j MLP layer j
+    (vtd_encoder_block_backward_dropout); site_base + j head layer j (vtd_head_backward_dropout)."""
     _fields_ = [("seed", ctypes.c_uint64), ("step", ctypes.c_uint64),
                 ("site_base", ctypes.c_uint32), ("rate", c_float)]
 
@@ -252,6 +253,10 @@ SIGNATURES = {
     "vtd_head_backward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdHeadParams),
                                   c_void_p, c_void_p, c_void_p, ctypes.POINTER(VtdHeadGrads),
                                   c_void_p, c_size_t, c_void_p]),
+    "vtd_head_backward_dropout": (c_int, [ctypes.POINTER(VtdConfig),
+                                          ctypes.POINTER(VtdHeadParams), c_void_p, c_void_p,
+                                          c_void_p, ctypes.POINTER(VtdHeadGrads), c_void_p,
+                                          c_size_t, c_void_p, ctypes.POINTER(VtdBlockDropout)]),
     "vtd_attention_train": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                     c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "vtd_attention_backward_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int,

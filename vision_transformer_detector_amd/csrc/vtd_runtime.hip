@@ -917,9 +917,22 @@ int head_mode(const vtd_config* cfg, vtd_dims* d, const char* what) {
 
 static int head_backward(const vtd_config* cfg, const vtd_head_params* w, const float* encoded,
                          const float* dlogits, float* logits_out, const vtd_head_grads* g,
-                         void* ws_, size_t ws_bytes, void* stream_) {
+                         void* ws_, size_t ws_bytes, void* stream_,
+                         const vtd_block_dropout* drop = nullptr) {
   vtd_dims d;
   if (int rc = head_mode(cfg, &d, "head_backward")) return rc;
+  // dropout (optional): site_base + j follows head layer j's activation, over the unpadded
+  // [B 17][units_j] plane.  The backward's recomputed forward regenerates the forward's masks
+  DropKey dk_head[VTD_MAX_HEAD]{};
+  bool drop_on = false;
+  if (drop) {
+    VTD_CHECK_ARG((uint64_t)drop->site_base + d.n_head <= 0xffffffffull,
+                  "head_backward_dropout: site_base + n_head overflows 32 bits");
+    for (int j = 0; j < d.n_head; ++j) {
+      const vtd_dropout dj{drop->seed, drop->step, drop->site_base + (uint32_t)j, drop->rate};
+      if (int rc = drop_prepare("head_backward_dropout", &dj, &dk_head[j], &drop_on)) return rc;
+    }
+  }
   VTD_CHECK_ARG(w && encoded && ws_ && (dlogits ? g != nullptr : logits_out != nullptr),
                 "head_backward: null pointer");
   const int nh = d.n_head;
@@ -1001,8 +1014,10 @@ static int head_backward(const vtd_config* cfg, const vtd_head_params* w, const 
     e.out = ws + P.z[j]; e.ldo = up; e.out_dtype = VTD_F32;
     if ((rc = gemm(HR, up, m.kk(k), a, m.ka(k), ws + P.wt, P.fwd_ks[j], e, 2.0 * HR * kv * uv)))
       return rc;
-    if ((rc = act_forward_launch(reinterpret_cast<const float*>(ws + P.z[j]), HR, uv, up, act,
-                                 ws + P.a[j], m.ka(up), op, st)))
+    const float* z = reinterpret_cast<const float*>(ws + P.z[j]);
+    if ((rc = drop_on ? act_forward_drop_launch(z, HR, uv, up, act, ws + P.a[j], m.ka(up), op,
+                                                dk_head[j], st)
+                      : act_forward_launch(z, HR, uv, up, act, ws + P.a[j], m.ka(up), op, st)))
       return rc;
     a = ws + P.a[j];
     k = up; kv = uv;
@@ -1040,8 +1055,10 @@ static int head_backward(const vtd_config* cfg, const vtd_head_params* w, const 
     const int up = d.head_units_p[j], uv = d.head_units[j];
     const int kin = j ? d.head_units_p[j - 1] : Tp, kinv = j ? d.head_units[j - 1] : T;
     const void* ain = j ? ws + P.a[j - 1] : u;
-    if ((rc = act_grad_launch(reinterpret_cast<const float*>(ws + P.z[j]), up, da[cur], up, HR, uv,
-                              act, gz, m.ka(up), op, st)))
+    const float* z = reinterpret_cast<const float*>(ws + P.z[j]);
+    if ((rc = drop_on ? act_grad_drop_launch(z, up, da[cur], up, HR, uv, act, gz, m.ka(up), op,
+                                             dk_head[j], st)
+                      : act_grad_launch(z, up, da[cur], up, HR, uv, act, gz, m.ka(up), op, st)))
       return rc;
     if ((rc = wgrad(HR, kinv, uv, ain, m.ka(kin), gz, m.ka(up), g->w_head[j], g->b_head[j],
                     P.wg_ms[j])))
@@ -1491,6 +1508,17 @@ int vtd_head_backward(const vtd_config* cfg, const vtd_head_params* w, const flo
                       const float* dlogits_dev, float* logits_dev, const vtd_head_grads* g,
                       void* ws, size_t ws_bytes, void* stream) {
   return head_backward(cfg, w, encoded_dev, dlogits_dev, logits_dev, g, ws, ws_bytes, stream);
+}
+
+int vtd_head_backward_dropout(const vtd_config* cfg, const vtd_head_params* w,
+                              const float* encoded_dev, const float* dlogits_dev,
+                              float* logits_dev, const vtd_head_grads* g, void* ws,
+                              size_t ws_bytes, void* stream, const vtd_block_dropout* drop) {
+  VTD_CHECK_ARG(drop, "head_backward_dropout: null dropout description");
+  VTD_CHECK_ARG(drop->rate >= 0.f && drop->rate < 1.f,
+                "head_backward_dropout: dropout rate must be in [0, 1)");   // NaN fails
+  return head_backward(cfg, w, encoded_dev, dlogits_dev, logits_dev, g, ws, ws_bytes, stream,
+                       drop);
 }
 
 }  // extern "C"

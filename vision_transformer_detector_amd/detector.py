@@ -159,6 +159,7 @@ class Model:
         self.loss = None               # compile(): the loss callable and the metric objects
         self.metrics = []
         self.optimizer = None          # compile(): stored as given, resolved by a training call
+        self.dropout_seed = None       # compile(dropout_seed=): dropout in the training graph
         self._head_dirty = False       # the head's device masters are ahead of self._master
         self._enc_dirty = False        # so are the encoder's and the stem's (train_on_batch)
         self.set_weights(keras_default_init(self.weight_shapes, seed))
@@ -513,14 +514,27 @@ class Model:
                                                                   np.float32)
 
     # ---- compile / evaluate (ipynb:408-435, 835; vtd.py:2172)
-    def compile(self, optimizer=None, loss=None, metrics=None, **_):
-        """keras.Model.compile: stores `optimizer`, `loss` and `metrics`.  `optimizer` is kept as
+    def compile(self, optimizer=None, loss=None, metrics=None, dropout_seed=None, **_):
+        """keras.Model.compile: stores `optimizer`, `loss`, `metrics` and `dropout_seed`.
+        `optimizer` is kept as
         given and never refused here -- optimizers.Adam or the string "adam" (= Adam()) train the
         head (train_head_on_batch, fit_head) or every weight (train_on_batch, fit); anything
         else raises only when a training call needs it.  `loss` is my_custom_loss or a
         functools.partial of it (its keywords are read off and evaluate runs the fused
         from-logits kernel), or any callable (y_true, logits) -> scalar, called per batch.
-        `metrics`: objects with update_state / result / reset_state (MeanAveragePrecision)."""
+        `metrics`: objects with update_state / result / reset_state (MeanAveragePrecision).
+        `dropout_seed` (an int below 2^64, kept as `model.dropout_seed`; None, the default, clears
+        it as a missing `loss` clears the loss): with it a model built with `dropout` > 0 applies
+        that dropout in the gradient and training calls -- every mask a function of (this seed,
+        the step, the site, the index) alone, DESIGN.md "Dropout" -- and without it those calls
+        run the dropout=None graph (train_on_batch / fit raise).  It changes nothing for a model
+        without dropout, and nothing in model(images), predict or evaluate."""
+        if dropout_seed is not None:
+            if isinstance(dropout_seed, bool) or not isinstance(dropout_seed, (int, np.integer)) \
+                    or not 0 <= int(dropout_seed) < 1 << 64:
+                raise ValueError(f"compile: dropout_seed must be an int in [0, 2^64), got "
+                                 f"{dropout_seed!r}")
+            dropout_seed = int(dropout_seed)
         if loss is not None and not callable(loss):
             raise TypeError(f"compile: loss must be callable, got {type(loss).__name__}")
         metrics = list(metrics or [])
@@ -532,6 +546,7 @@ class Model:
             from .optimizers import Adam
             optimizer = Adam()
         self.loss, self.metrics, self.optimizer = loss, metrics, optimizer
+        self.dropout_seed = dropout_seed
 
     def _evaluate_batches(self, x, y, batch_size):
         if y is None:
@@ -669,7 +684,95 @@ class Model:
         """The device masters of the head's weights (vtd_head_params)."""
         return self._device_master("head", self.head_weight_names())
 
-    def head_gradients(self, images, y_true, encoded=None):
+    def head_weights(self):
+        """The weights of the detection head as `detection_head` takes them: an OrderedDict of
+        Keras name -> fp32 device tensor in the Keras shape, in creation order
+        (`head_weight_names()`).  Fresh copies of the model's current weights, as
+        `stem_weights` returns the stem's."""
+        return OrderedDict((n, t.clone()) for n, t in self._head_master().items())
+
+    def detection_head(self, encoded, weights=None, *, seed=None, step=0, dropout=None,
+                       site_base=None):
+        """The detection head (mlp_head, vtd.py:454-493) as a differentiable op: logits
+        (B, 17, 6) from `encoded` (B, N, d), a float32 device tensor.  backward() fills
+        encoded.grad and the gradient of every tensor of `weights` that requires grad.
+        `weights`: the head's tensors in creation order and Keras shapes (a sequence, or a dict
+        whose values are taken; `head_weights()` returns them so); None: the model's current
+        head weights.  The forward is vtd_head_backward's forward-only call, the backward one
+        forward + backward call; so patch_embedding -> encoder_block x L -> detection_head ->
+        my_custom_loss is one autograd chain.
+
+        Dropout: `seed` None is the dropout=None head, bit for bit.  With a seed, `dropout`
+        (default: the rate the model was built with) follows every head Dense + activation --
+        none after Dense(17) or MLP_Head_no_Sigmoid -- head layer j at site `site_base + j`
+        (default site_base: encoder_repeat_times * (1 + encoder_mlp_quantities), after the
+        blocks' sites), over the unpadded [B 17][units_j] activation; the backward regenerates
+        the forward's masks from (seed, step, site).  A positive `dropout` given without a seed
+        raises.  Needs dtype 'bf16x3' or 'bfloat16'."""
+        from . import head as _head
+        from .dropout import spec
+        what = "detection_head"
+        self._require(what, loss=False)
+        dims = self.dims
+        if not torch.is_tensor(encoded) or not encoded.is_cuda or encoded.dtype != torch.float32:
+            raise ValueError(f"{what}: encoded must be a float32 device tensor")
+        if encoded.dim() != 3 or tuple(encoded.shape[1:]) != (dims.tokens, dims.d) \
+                or encoded.shape[0] < 1:
+            raise ValueError(f"{what}: encoded must be (B, {dims.tokens}, {dims.d}), got "
+                             f"{tuple(encoded.shape)}")
+        names = self.head_weight_names()
+        if weights is None:
+            weights = list(self._head_master().values())
+        else:
+            weights = list(weights.values()) if isinstance(weights, dict) else list(weights)
+            if len(weights) != len(names):
+                raise ValueError(f"{what}: weights must hold {len(names)} tensors "
+                                 f"({', '.join(names)}), got {len(weights)}")
+            for n, t in zip(names, weights):
+                if not torch.is_tensor(t) or t.dtype != torch.float32 \
+                        or t.device != encoded.device:
+                    raise ValueError(f"{what}: {n} must be a float32 tensor on encoded's device")
+                if tuple(t.shape) != tuple(self.weight_shapes[n]):
+                    raise ValueError(f"{what}: {n} has shape {tuple(t.shape)}, expected "
+                                     f"{self.weight_shapes[n]}")
+        if dropout is None and seed is not None:
+            dropout = self.kwargs.get("dropout")
+        if site_base is None:
+            site_base = self._head_site_base()
+        d1 = spec(what, dropout, seed, step, site_base)
+        drop = None
+        if d1 is not None:
+            if int(site_base) + dims.n_head >= 1 << 32:
+                raise ValueError(f"{what}: site_base + the head's layers must fit 32 bits")
+            drop = L.VtdBlockDropout(seed=d1.seed, step=d1.step, site_base=d1.site, rate=d1.rate)
+        return _head.DetectionHead.apply(encoded.contiguous(),
+                                         (self.config(encoded.shape[0]), drop), *weights)
+
+    # ---- dropout in the gradient and training calls (compile(dropout_seed=))
+    def _head_site_base(self):
+        """The head's first dropout site: after block i's site_base = i * (1 + q)."""
+        return self.kwargs["encoder_repeat_times"] * (1 + self.kwargs["encoder_mlp_quantities"])
+
+    def _call_dropout(self, what, step):
+        """The dropout of one gradient / training call: None -- a model without dropout, or no
+        compiled seed -- or (rate, seed, step)."""
+        rate = self.kwargs.get("dropout")
+        if not rate or self.dropout_seed is None:
+            return None
+        from .dropout import spec
+        d1 = spec(what, rate, self.dropout_seed, step)
+        return d1.rate, d1.seed, d1.step
+
+    def _site_dropout(self, drop, block=None):
+        """The VtdBlockDropout of encoder block `block` (site_base = block * (1 + q)), or of the
+        head (block=None), for a `_call_dropout` result; None for None."""
+        if drop is None:
+            return None
+        base = (self._head_site_base() if block is None
+                else block * (1 + self.kwargs["encoder_mlp_quantities"]))
+        return L.VtdBlockDropout(seed=drop[1], step=drop[2], site_base=base, rate=drop[0])
+
+    def head_gradients(self, images, y_true, encoded=None, step=0):
         """One frozen-encoder training step up to the optimizer update: encoder features ->
         head -> compiled loss -> gradients.  Returns (out5, grads): out5 as loss_and_grad
         returns it (total, objectness, class, CIoU means, positives) and `grads` an OrderedDict
@@ -677,9 +780,12 @@ class Model:
         plus "encoded_images" (B, N, d) = d loss / d encoded_images, where an encoder backward
         would start.  `encoded`: the (B, N, d) output of `encode` -- the cached-features use,
         `images` is then ignored.  The logits gradient is vtd_loss_grad's, the rest
-        vtd_head_backward.  Needs compile(loss=my_custom_loss or a functools.partial of it) and
-        dtype 'bf16x3' or 'bfloat16'."""
-        return self._head_pass("head_gradients", images, y_true, encoded)
+        vtd_head_backward.  On a model built with `dropout` and compiled with a `dropout_seed`
+        the head's dropout sites are on, masks of (seed, `step`, site) -- the encoder stays the
+        inference forward; otherwise `step` is not used.  Needs compile(loss=my_custom_loss or a
+        functools.partial of it) and dtype 'bf16x3' or 'bfloat16'."""
+        return self._head_pass("head_gradients", images, y_true, encoded,
+                               drop=self._call_dropout("head_gradients", step))
 
     # ---- whole-model gradients (vtd_stem_backward, vtd_encoder_block_backward, vtd_head_backward)
     def stem_weights(self):
@@ -696,7 +802,7 @@ class Model:
         names = list(self.weight_shapes)[:3 + self.kwargs["encoder_repeat_times"] * per]
         return self._device_master("encoder", names)
 
-    def gradients(self, images, y_true):
+    def gradients(self, images, y_true, step=0):
         """The gradient of the compiled loss with respect to every weight: the training forward
         of the whole model, the loss gradient at its logits, and the backward through the head,
         every encoder block in reverse and the patch embedding.  Returns (out5, grads): out5 as
@@ -709,15 +815,22 @@ class Model:
         the current stream with no host read: vtd_stem_backward (forward only),
         vtd_encoder_block_backward per block (forward only, every block input kept),
         head_gradients' pass on the last block's output, then the blocks' backward calls in
-        reverse through one shared workspace and the stem's.  Needs compile(loss=my_custom_loss
-        or a functools.partial of it) and dtype 'bf16x3' or 'bfloat16'."""
-        return self._grad_chain("gradients", images, y_true)
+        reverse through one shared workspace and the stem's.  On a model built with `dropout`
+        and compiled with a `dropout_seed` every dropout site of the reference's training graph
+        is on (vtd_encoder_block_backward_dropout with site_base = i (1 + q) for block i,
+        vtd_head_backward_dropout with site_base = L (1 + q)), the masks those of (seed, `step`,
+        site): the same step gives the same bits; otherwise `step` is not used.  Needs
+        compile(loss=my_custom_loss or a functools.partial of it) and dtype 'bf16x3' or
+        'bfloat16'."""
+        return self._grad_chain("gradients", images, y_true, step=step)
 
-    def _grad_chain(self, what, images, y_true, buffers=None):
+    def _grad_chain(self, what, images, y_true, buffers=None, step=0):
         """The chain gradients and train_on_batch share.  `buffers`: Keras name -> fp32 device
         tensor to write each weight gradient into (the optimizer's persistent ones); None
-        allocates fresh tensors.  Returns (out5, grads keyed by `weight_names()`)."""
+        allocates fresh tensors.  `step`: the dropout step (`_call_dropout`).  Returns (out5,
+        grads keyed by `weight_names()`)."""
         self._require(what)
+        drop = self._call_dropout(what, step)
         from . import encoder as _enc
         from . import stem as _stem
         x = self._as_images(images)
@@ -743,22 +856,24 @@ class Model:
             sw = wdev[:3]
             bw = [wdev[3 + i * per: 3 + (i + 1) * per] for i in range(reps)]
             xs = [_stem.run(x, sw, sdims, ws=stem_ws)[0]]
+            bdrop = [self._site_dropout(drop, i) for i in range(reps)]
             for i in range(reps):
-                xs.append(_enc.run(xs[i], bw[i], bdims, ws=block_ws)[0])
+                xs.append(_enc.run(xs[i], bw[i], bdims, ws=block_ws, drop=bdrop[i])[0])
             names = list(self.weight_shapes)
             into = None if buffers is None else [buffers[n] for n in names]
             head_into = None
             if into is not None:
                 head_into = OrderedDict(zip(names[3 + reps * per:], into[3 + reps * per:]))
                 head_into["encoded_images"] = torch.empty_like(xs[reps])
-            out5, head = self._head_pass(what, None, y_true, xs[reps], weight_grads=head_into)
+            out5, head = self._head_pass(what, None, y_true, xs[reps], weight_grads=head_into,
+                                         drop=drop)
             head = OrderedDict(head)
             dy = head.pop("encoded_images")
             found = []
             for i in range(reps - 1, -1, -1):
                 out = None if into is None else (None, into[3 + i * per: 3 + (i + 1) * per], None)
                 _, g, dy = _enc.run(xs[i], bw[i], bdims, dy=dy, want_y=False, ws=block_ws,
-                                    out=out)
+                                    out=out, drop=bdrop[i])
                 found = g + found
             _, g = _stem.run(x, sw, sdims, dx0=dy, want_x0=False, ws=stem_ws,
                              out=None if into is None else (None, into[:3]))
@@ -769,15 +884,18 @@ class Model:
     def _require(self, what, mode=True, loss=True, optimizer=False, whole_model=False):
         """The preconditions of the gradient and training calls, for the caller `what`, in this
         order: the mode (`mode`), for whole-model training (`whole_model`) a model without
-        dropout, a compiled fused loss (`loss`), a resolvable compiled optimizer (`optimizer`).
-        Returns (the fused loss parameters, the optimizer), None where not asked for."""
+        dropout or with a compiled dropout seed, a compiled fused loss (`loss`), a resolvable
+        compiled optimizer (`optimizer`).  Returns (the fused loss parameters, the optimizer), None where not asked for."""
         if mode and self.dtype not in (L.BF16X3, L.BF16):
             does = "model trains" if whole_model else "head backward runs"
             raise ValueError(f"{what}: the {does} in the 'bf16x3' and 'bfloat16' modes only "
                              "(not float32 / float8)")
-        if whole_model and self.kwargs.get("dropout"):
-            raise ValueError(f"{what}: the training graph here is the dropout=None graph; this "
-                             f"model was built with dropout={self.kwargs['dropout']!r}")
+        if whole_model and self.kwargs.get("dropout") and self.dropout_seed is None:
+            raise ValueError(f"{what}: this model was built with dropout="
+                             f"{self.kwargs['dropout']!r} and no dropout seed is compiled; "
+                             "compile(..., dropout_seed=<int>) trains it with that dropout (no "
+                             "implicit randomness: the masks are a function of the seed and the "
+                             "step)")
         params = resolved = None
         if loss:
             from . import loss as _loss
@@ -843,10 +961,13 @@ class Model:
         back.  Afterwards the device masters are the truth for every tensor; get_weights /
         get_weight_dict / save_weights read them back on demand.  Needs
         compile(optimizer=optimizers.Adam(...) or 'adam', loss=my_custom_loss or a
-        functools.partial of it), dtype 'bf16x3' or 'bfloat16' and a model without dropout."""
+        functools.partial of it) and dtype 'bf16x3' or 'bfloat16'; a model built with `dropout`
+        also needs compile(dropout_seed=...), and its masks take `optimizer.iterations` as read
+        before the step for the dropout step: 0 for the first step, one more per step."""
         _, optimizer = self._require("train_on_batch", optimizer=True, whole_model=True)
-        out5, _ = self._grad_chain("train_on_batch", images, y_true,
-                                   optimizer.gradient_buffers(self, scope="all"))
+        buffers = optimizer.gradient_buffers(self, scope="all")   # (a fresh state counts from 0)
+        out5, _ = self._grad_chain("train_on_batch", images, y_true, buffers,
+                                   step=optimizer.iterations)
         optimizer.apply(self, scope="all")
         return out5
 
@@ -877,13 +998,16 @@ class Model:
         Returns out5 as head_gradients does, taken before the update, as Keras reports the
         loss; nothing is read back to the host.  Afterwards the device masters
         (`_head_master()`) are the truth for the head; get_weights / get_weight_dict /
-        save_weights read them back on demand.  Needs compile(optimizer=optimizers.Adam(...) or
-        'adam', loss=my_custom_loss or a functools.partial of it) and dtype 'bf16x3' or
-        'bfloat16'."""
+        save_weights read them back on demand.  With `dropout` and a compiled `dropout_seed` the
+        head's dropout sites are on, the dropout step `optimizer.iterations` as read before the
+        step.  Needs compile(optimizer=optimizers.Adam(...) or 'adam', loss=my_custom_loss or a
+        functools.partial of it) and dtype 'bf16x3' or 'bfloat16'."""
         # the compiled loss is _head_pass's check: a missing optimizer is reported first
         _, optimizer = self._require("train_head_on_batch", loss=False, optimizer=True)
-        out5, _ = self._head_pass("train_head_on_batch", images, y_true, encoded,
-                                  weight_grads=optimizer.gradient_buffers(self, scope="head"))
+        buffers = optimizer.gradient_buffers(self, scope="head")  # (a fresh state counts from 0)
+        out5, _ = self._head_pass(
+            "train_head_on_batch", images, y_true, encoded, weight_grads=buffers,
+            drop=self._call_dropout("train_head_on_batch", optimizer.iterations))
         optimizer.apply(self, scope="head")
         return out5
 
@@ -920,12 +1044,14 @@ class Model:
             return self.train_head_on_batch(images, labels, encoded=feats)
         return self._fit_loop("fit_head", optimizer, batches, step, epochs, lr_schedule)
 
-    def _head_pass(self, what, images, y_true, encoded, weight_grads=None):
+    def _head_pass(self, what, images, y_true, encoded, weight_grads=None, drop=None):
         """The part head_gradients and train_head_on_batch share: the checks, the encoder
         features, the training forward for the logits, the loss gradient there, and the
         backward.  `weight_grads`: buffers to write the weight gradients into (the optimizer's
         persistent ones; d loss / d encoded_images is then not computed); None allocates them
-        and the encoded_images gradient.  Returns (out5, grads)."""
+        and the encoded_images gradient.  `drop`: the call's dropout (`_call_dropout`): the
+        head's sites of both chain calls.  Returns (out5, grads)."""
+        from . import head as _head
         from . import loss as _loss
         params, _ = self._require(what)
         dims = self.dims
@@ -940,39 +1066,24 @@ class Model:
                                      f"{dims.d}), got {tuple(encoded.shape)}")
             b = encoded.shape[0]
             cfg = self.config(b)
-            need = ctypes.c_size_t()
-            L.check(L.lib.vtd_head_backward_workspace_bytes(ctypes.byref(cfg), ctypes.byref(need)),
-                    "head_backward_workspace_bytes")
-            if getattr(self, "_hb_ws", None) is None or self._hb_ws.numel() < need.value:
-                self._hb_ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            need = _head.workspace_bytes(cfg)
+            if getattr(self, "_hb_ws", None) is None or self._hb_ws.numel() < need:
+                self._hb_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             wdev = self._head_master()
             if weight_grads is None:
                 grads = OrderedDict((n, torch.empty_like(t)) for n, t in wdev.items())
                 grads["encoded_images"] = torch.empty_like(encoded)
             else:
                 grads = weight_grads
-            P, G = L.VtdHeadParams(), L.VtdHeadGrads()
-            for S, src in ((P, wdev), (G, grads)):
-                S.w_det, S.b_det = src["dense/kernel"].data_ptr(), src["dense/bias"].data_ptr()
-                for j in range(dims.n_head):
-                    S.w_head[j] = src[f"dense_{j + 1}/kernel"].data_ptr()
-                    S.b_head[j] = src[f"dense_{j + 1}/bias"].data_ptr()
-                S.w_final = src["MLP_Head_no_Sigmoid/kernel"].data_ptr()
-                S.b_final = src["MLP_Head_no_Sigmoid/bias"].data_ptr()
-            G.d_encoded = L.ptr(grads.get("encoded_images"))
-            st = L.stream_ptr()
+            weights = list(wdev.values())
+            hdrop = self._site_dropout(drop)
             # the training forward alone for its logits, the loss gradient at those logits,
-            # then the forward again with the backward
+            # then the forward again with the backward (with dropout: the same masks again)
             logits = torch.empty((b, L.MAX_DETECT, 6), dtype=torch.float32, device=self.device)
-            L.check(L.lib.vtd_head_backward(ctypes.byref(cfg), ctypes.byref(P), encoded.data_ptr(),
-                                            None, logits.data_ptr(), None,
-                                            self._hb_ws.data_ptr(), self._hb_ws.numel(), st),
-                    "vtd_head_backward")
+            _head.run(cfg, encoded, weights, logits=logits, ws=self._hb_ws, drop=hdrop)
             out5, dlogits = _loss.loss_and_grad(y_true, logits, params=params)
-            L.check(L.lib.vtd_head_backward(ctypes.byref(cfg), ctypes.byref(P), encoded.data_ptr(),
-                                            dlogits.data_ptr(), None, ctypes.byref(G),
-                                            self._hb_ws.data_ptr(), self._hb_ws.numel(), st),
-                    "vtd_head_backward")
+            _head.run(cfg, encoded, weights, dlogits=dlogits, grads=[grads[n] for n in wdev],
+                      d_encoded=grads.get("encoded_images"), ws=self._hb_ws, drop=hdrop)
         return out5, grads
 
     def count_params(self) -> int:
@@ -1002,7 +1113,8 @@ def create_vision_transformer_detector(
     is the identity at inference -- those layers run with the call's `training` flag, False
     in `model(x, training=False)` / `predict` -- and Dropout has no weights, so any rate in
     [0, 1) builds the same forward and the same weight names; only a build-time
-    `training=True` (dropout forced on in every call) is refused.  `max_weight`/`clip_weight` are weight constraints
+    `training=True` (dropout forced on in every call) is refused.  The gradient and training calls
+    apply a rate > 0 once `compile(..., dropout_seed=<int>)` names a seed (Model.compile).  `max_weight`/`clip_weight` are weight constraints
     Keras applies only after optimizer steps (vtd.py:209-236), so they do not affect
     the forward; train_head_on_batch / fit_head apply them after every step.  Extra keyword-only options: `dtype`, `device`,
     `seed`.  `dtype` defaults to 'bf16x3', the split-bf16 parity mode: every product as three
