@@ -12,8 +12,17 @@ Block scale rule (vtd_mx8.hip): the least power of two 2^E with amax <= 448 * 2^
 E clamped to [-126, 126] (E = -126 for an all-zero block).
 Scale layout: s[k // 128][row][4] (the four 32-blocks of one 128-wide K-step of a row
 form one dword).  Parity unpinned against any reference output (none exists); the GPU
-tests check the device quantizer against this restatement element for element and the
-MX GEMM against the fp64 product of the dequantized operands.
+tests check the device quantizer against this restatement byte for byte (encode_e4m3) and
+the MX GEMM against the fp64 product of the dequantized operands.
+
+Zero and subnormals follow IEEE: the sign survives an underflow (a negative element below
+2^-10 after scaling, and -0, encode as 0x80), and f32-subnormal inputs are kept (a block
+whose amax is subnormal has E = -126, its elements are multiplied by 2^126 and rounded as
+any other value).  Observed on an MI355X through vtd_quantize_mx8 on the designed blocks of
+tests/mx_designs.py (tests/test_gpu_mx8_designed.py): v_cvt_pk_fp8_f32 writes 0x80 for a
+negative value that underflows and for -0, never 0x00, and the kernel's multiply by 2^-E
+flushes nothing -- the device bytes equal this module's for both source dtypes.  Both
+bytes decode to zero, so no GEMM result depends on it.
 """
 import numpy as np
 
@@ -41,7 +50,7 @@ def round_e4m3(v):
     e = np.maximum(e, -6.0)                     # subnormals share the 2^-6 binade's quantum
     quantum = np.exp2(e - 3.0)
     r = np.rint(a / quantum) * quantum          # np.rint: half to even
-    return np.sign(v) * r
+    return np.copysign(r, v)                    # the sign survives an underflow to zero
 
 
 def decode_e4m3(b):
@@ -53,6 +62,16 @@ def decode_e4m3(b):
     val = np.where(E == 0, m * 2.0 ** -9, (1.0 + m / 8.0) * np.exp2(E - 7.0))
     val = np.where((E == 15) & (m == 7), np.nan, val)
     return s * val
+
+
+def encode_e4m3(vals):
+    """e4m3 values (as quantize returns them) -> bytes; the sign bit of -0 is kept."""
+    vals = np.asarray(vals, np.float64)
+    mag = np.abs(vals)
+    table = decode_e4m3(np.arange(127, dtype=np.uint8))          # 0x7f: NaN
+    idx = np.searchsorted(table, mag)
+    assert np.array_equal(table[np.minimum(idx, 126)], mag), "not an e4m3 value"
+    return (idx | (np.signbit(vals).astype(np.int64) << 7)).astype(np.uint8)
 
 
 def quantize(x, Kq=None):

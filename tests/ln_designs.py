@@ -403,16 +403,7 @@ def split_expected(y_f32, P):
 
 
 # ------------------------------------------------------------------ MX-fp8
-_E4M3 = MX.decode_e4m3(np.arange(128, dtype=np.uint8))          # 0x7f: NaN
-
-
-def encode_e4m3(vals):
-    """e4m3 values (as MX.quantize returns them) -> bytes; the sign bit of -0 is kept."""
-    vals = np.asarray(vals, np.float64)
-    mag = np.abs(vals)
-    idx = np.searchsorted(_E4M3[:127], mag)
-    assert np.array_equal(_E4M3[:127][np.minimum(idx, 126)], mag), "not an e4m3 value"
-    return (idx | (np.signbit(vals).astype(np.int64) << 7)).astype(np.uint8)
+encode_e4m3 = MX.encode_e4m3       # e4m3 values -> bytes; the sign bit of -0 is kept
 
 
 def mx_expected(vals, Kq):
@@ -462,7 +453,7 @@ def mx_beta(D, rng):
         pos = j % 32
         if 32 * j + pos >= D:
             pos = D - 1 - 32 * j
-        blk[pos] = amax if j % 2 == 0 else -amax
+        blk[pos] = amax if j % 2 == 0 or amax == 0 else -amax       # never -0: y = +0 + beta
         beta[32 * j:32 * j + 32] = blk
     beta = beta[:D].astype(f32)
     assert np.array_equal(bf16_value(bf16_bits(beta)), beta)
