@@ -1971,54 +1971,9 @@ int attention_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqk
 // vtd_attention_train: the streaming kernels vtd_attention runs (VTD_BF16X3 at the default;
 // VTD_BF16 as under VTD_KNOB_ATTN_VARIANT 2: 4 waves up to N = 128, else 8), instantiated with
 // LSE, so O has the same bits and lse comes from the same statistics.
-int attention_train_drop_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
-                                float scale, void* out, int ldo, float* lse, int dtype,
-                                const DropKey& dk, hipStream_t stream) {
-  VTD_CHECK_ARG(qkv && out && lse, "attention_train_dropout: null pointer");
-  VTD_CHECK_ARG(B > 0 && N > 0 && heads > 0, "attention_train_dropout: bad B/N/heads");
-  VTD_CHECK_ARG(dkp == 32 || dkp == 64 || dkp == 128,
-                "attention_train_dropout: dkp must be 32/64/128");
-  VTD_CHECK_ARG(scale > 0 && std::isfinite(scale),
-                "attention_train_dropout: scale must be positive and finite");
-  if (dtype != VTD_BF16 && dtype != VTD_BF16X3)
-    return fail(VTD_ERR_UNSUPPORTED,
-                "attention_train_dropout: dtype must be VTD_BF16 or VTD_BF16X3");
-  const bool x3 = dtype == VTD_BF16X3;
-  VTD_CHECK_ARG(!x3 || ldo % 2 == 0,
-                "attention_train_dropout: a split-bf16 output needs ldo % 2 == 0");
-  const int owidth = x3 ? ldo / 2 : ldo;
-  VTD_CHECK_ARG(ldqkv >= 3 * heads * dkp && owidth >= heads * dkp,
-                "attention_train_dropout: leading dimensions too small");
-  VTD_CHECK_ARG(ldqkv % 8 == 0 && owidth % 8 == 0,
-                "attention_train_dropout: ld must be multiple of 8");
-  ProfScope ps(stream, PROF_ATTN, 4.0 * B * heads * (double)N * N * dkp);
-  // the variants vtd_attention_train picks (its knob included), so that the statistics and the
-  // LSE are computed by the same instructions
-  if (x3) {
-    if (dkp == 32)
-      return launch_x3_drop<32, 64, 1>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk);
-    if (dkp == 64 && knob(VTD_KNOB_ATTN_VARIANT) != 10)
-      return launch_x3_drop<64, 32, 2>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk);
-    if (dkp == 64)
-      return launch_x3_drop<64, 64, 1>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk);
-    return launch_x3_drop<128, 64, 1>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk);
-  }
-#define VTD_TRAIN_DROP(D, W) \
-  launch_bf16_drop<D, W>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, dk)
-  if (N > 128) {
-    if (dkp == 32) return VTD_TRAIN_DROP(32, 8);
-    if (dkp == 64) return VTD_TRAIN_DROP(64, 8);
-    return VTD_TRAIN_DROP(128, 8);
-  }
-  if (dkp == 32) return VTD_TRAIN_DROP(32, 4);
-  if (dkp == 64) return VTD_TRAIN_DROP(64, 4);
-  return VTD_TRAIN_DROP(128, 4);
-#undef VTD_TRAIN_DROP
-}
-
 int attention_train_launch(const void* qkv, int B, int N, int heads, int dkp, int ldqkv,
                            float scale, void* out, int ldo, float* lse, int dtype,
-                           hipStream_t stream) {
+                           hipStream_t stream, const DropKey* dk) {
   VTD_CHECK_ARG(qkv && out && lse, "attention_train: null pointer");
   VTD_CHECK_ARG(B > 0 && N > 0 && heads > 0, "attention_train: bad B/N/heads");
   VTD_CHECK_ARG(dkp == 32 || dkp == 64 || dkp == 128, "attention_train: dkp must be 32/64/128");
@@ -2033,17 +1988,21 @@ int attention_train_launch(const void* qkv, int B, int N, int heads, int dkp, in
                 "attention_train: leading dimensions too small");
   VTD_CHECK_ARG(ldqkv % 8 == 0 && owidth % 8 == 0, "attention_train: ld must be multiple of 8");
   ProfScope ps(stream, PROF_ATTN, 4.0 * B * heads * (double)N * N * dkp);
+  // dk: the DROP instantiations of the same variants (the knob included), so that the statistics
+  // and the LSE are computed by the same instructions
+#define VTD_TRAIN_X3(...)                                                                        \
+  (dk ? launch_x3_drop<__VA_ARGS__>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, *dk)  \
+      : launch_x3<__VA_ARGS__, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse))
+#define VTD_TRAIN_BF16(D, W)                                                                     \
+  (dk ? launch_bf16_drop<D, W>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse, *dk)       \
+      : launch_bf16_v2<D, W, false, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream,      \
+                                          nullptr, 0, lse))
   if (x3) {
-    if (dkp == 32)
-      return launch_x3<32, 64, 1, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse);
-    if (dkp == 64 && knob(VTD_KNOB_ATTN_VARIANT) != 10)
-      return launch_x3<64, 32, 2, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse);
-    if (dkp == 64)
-      return launch_x3<64, 64, 1, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse);
-    return launch_x3<128, 64, 1, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, lse);
+    if (dkp == 32) return VTD_TRAIN_X3(32, 64, 1);
+    if (dkp == 64 && knob(VTD_KNOB_ATTN_VARIANT) != 10) return VTD_TRAIN_X3(64, 32, 2);
+    if (dkp == 64) return VTD_TRAIN_X3(64, 64, 1);
+    return VTD_TRAIN_X3(128, 64, 1);
   }
-#define VTD_TRAIN_BF16(D, W) \
-  launch_bf16_v2<D, W, false, true>(qkv, B, N, heads, ldqkv, scale, out, ldo, stream, nullptr, 0, lse)
   if (N > 128) {
     if (dkp == 32) return VTD_TRAIN_BF16(32, 8);
     if (dkp == 64) return VTD_TRAIN_BF16(64, 8);
@@ -2052,6 +2011,7 @@ int attention_train_launch(const void* qkv, int B, int N, int heads, int dkp, in
   if (dkp == 32) return VTD_TRAIN_BF16(32, 4);
   if (dkp == 64) return VTD_TRAIN_BF16(64, 4);
   return VTD_TRAIN_BF16(128, 4);
+#undef VTD_TRAIN_X3
 #undef VTD_TRAIN_BF16
 }
 
@@ -2116,9 +2076,7 @@ extern "C" int vtd_attention_train_dropout(const void* qkv_dev, int B, int N, in
   vtd::DropKey dk;
   bool on;
   if (int rc = vtd::drop_prepare("vtd_attention_train_dropout", drop, &dk, &on)) return rc;
-  if (!on)
-    return vtd::attention_train_launch(qkv_dev, B, N, heads, dkp, ldqkv, scale, out_dev, ldo,
-                                       lse_dev, dtype, static_cast<hipStream_t>(stream));
-  return vtd::attention_train_drop_launch(qkv_dev, B, N, heads, dkp, ldqkv, scale, out_dev, ldo,
-                                          lse_dev, dtype, dk, static_cast<hipStream_t>(stream));
+  return vtd::attention_train_launch(qkv_dev, B, N, heads, dkp, ldqkv, scale, out_dev, ldo,
+                                     lse_dev, dtype, static_cast<hipStream_t>(stream),
+                                     on ? &dk : nullptr);
 }

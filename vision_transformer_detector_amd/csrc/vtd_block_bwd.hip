@@ -1,4 +1,4 @@
-// The pieces of vtd_encoder_block_backward (vtd_runtime.hip) that no other kernel covers: the
+// The pieces of vtd_encoder_block_backward (vtd_train_runtime.hip) that no other kernel covers: the
 // gather of the Keras attention kernels into the operand forms of the fused, per-head padded
 // matrices, the un-gather of the fused gradients back into the Keras shapes, and the block's
 // last step y = x1 + act(z).  All of them move at most a few MB per call (the last one a

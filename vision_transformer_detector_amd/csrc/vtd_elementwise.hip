@@ -1303,30 +1303,41 @@ int unpad_f32_launch(const void* x, int x_dtype, int64_t rows, int D, int ldx, f
 }
 
 int act_forward_launch(const float* z, int64_t rows, int N, int ldz, int act, void* y, int ldy,
-                       int dtype, hipStream_t st) {
+                       int dtype, hipStream_t st, const DropKey* dk) {
   VTD_CHECK_ARG(z && y && rows > 0 && N > 0 && ldz >= N, "act_forward: bad arguments");
   VTD_CHECK_ARG(act >= VTD_ACT_NONE && act <= VTD_ACT_MISH, "act_forward: unknown activation");
   int P;
   if (int rc = op_form("act_forward", y, ldy, dtype, N, &P)) return rc;
+  const dim3 grid(op_grid(rows * (P / 8)));
+  const int x3 = dtype == VTD_BF16X3 ? 1 : 0;
   ProfScope ps(st, PROF_OTHER, 0.0);
-  hipLaunchKernelGGL(act_op_kernel<0>, dim3(op_grid(rows * (P / 8))), dim3(256), 0, st, z, ldz,
-                     (const float*)nullptr, 0, rows, N, act, static_cast<bf16_t*>(y), ldy, P,
-                     dtype == VTD_BF16X3 ? 1 : 0);
+  if (dk)
+    hipLaunchKernelGGL(act_op_drop_kernel<0>, grid, dim3(256), 0, st, z, ldz,
+                       (const float*)nullptr, 0, rows, N, act, static_cast<bf16_t*>(y), ldy, P, x3,
+                       *dk);
+  else
+    hipLaunchKernelGGL(act_op_kernel<0>, grid, dim3(256), 0, st, z, ldz, (const float*)nullptr, 0,
+                       rows, N, act, static_cast<bf16_t*>(y), ldy, P, x3);
   VTD_LAUNCH_CHECK("act_forward");
   return VTD_OK;
 }
 
 int act_grad_launch(const float* z, int ldz, const float* ga, int ldga, int64_t rows, int N,
-                    int act, void* y, int ldy, int dtype, hipStream_t st) {
+                    int act, void* y, int ldy, int dtype, hipStream_t st, const DropKey* dk) {
   VTD_CHECK_ARG(z && ga && y && rows > 0 && N > 0 && ldz >= N && ldga >= N,
                 "act_grad: bad arguments");
   VTD_CHECK_ARG(act >= VTD_ACT_NONE && act <= VTD_ACT_MISH, "act_grad: unknown activation");
   int P;
   if (int rc = op_form("act_grad", y, ldy, dtype, N, &P)) return rc;
+  const dim3 grid(op_grid(rows * (P / 8)));
+  const int x3 = dtype == VTD_BF16X3 ? 1 : 0;
   ProfScope ps(st, PROF_OTHER, 0.0);
-  hipLaunchKernelGGL(act_op_kernel<1>, dim3(op_grid(rows * (P / 8))), dim3(256), 0, st, z, ldz,
-                     ga, ldga, rows, N, act, static_cast<bf16_t*>(y), ldy, P,
-                     dtype == VTD_BF16X3 ? 1 : 0);
+  if (dk)
+    hipLaunchKernelGGL(act_op_drop_kernel<1>, grid, dim3(256), 0, st, z, ldz, ga, ldga, rows, N,
+                       act, static_cast<bf16_t*>(y), ldy, P, x3, *dk);
+  else
+    hipLaunchKernelGGL(act_op_kernel<1>, grid, dim3(256), 0, st, z, ldz, ga, ldga, rows, N, act,
+                       static_cast<bf16_t*>(y), ldy, P, x3);
   VTD_LAUNCH_CHECK("act_grad");
   return VTD_OK;
 }
@@ -1337,36 +1348,6 @@ int drop_prepare(const char* what, const vtd_dropout* d, DropKey* key, bool* on)
   VTD_CHECK_ARG(d->rate >= 0.f && d->rate < 1.f, w + ": dropout rate must be in [0, 1)");   // NaN fails
   *on = d->rate > 0.f;
   *key = drop_key(d->seed, d->step, d->site, d->rate);
-  return VTD_OK;
-}
-
-int act_forward_drop_launch(const float* z, int64_t rows, int N, int ldz, int act, void* y, int ldy,
-                            int dtype, const DropKey& dk, hipStream_t st) {
-  VTD_CHECK_ARG(z && y && rows > 0 && N > 0 && ldz >= N, "act_forward_dropout: bad arguments");
-  VTD_CHECK_ARG(act >= VTD_ACT_NONE && act <= VTD_ACT_MISH,
-                "act_forward_dropout: unknown activation");
-  int P;
-  if (int rc = op_form("act_forward_dropout", y, ldy, dtype, N, &P)) return rc;
-  ProfScope ps(st, PROF_OTHER, 0.0);
-  hipLaunchKernelGGL(act_op_drop_kernel<0>, dim3(op_grid(rows * (P / 8))), dim3(256), 0, st, z, ldz,
-                     (const float*)nullptr, 0, rows, N, act, static_cast<bf16_t*>(y), ldy, P,
-                     dtype == VTD_BF16X3 ? 1 : 0, dk);
-  VTD_LAUNCH_CHECK("act_forward_dropout");
-  return VTD_OK;
-}
-
-int act_grad_drop_launch(const float* z, int ldz, const float* ga, int ldga, int64_t rows, int N,
-                         int act, void* y, int ldy, int dtype, const DropKey& dk, hipStream_t st) {
-  VTD_CHECK_ARG(z && ga && y && rows > 0 && N > 0 && ldz >= N && ldga >= N,
-                "act_grad_dropout: bad arguments");
-  VTD_CHECK_ARG(act >= VTD_ACT_NONE && act <= VTD_ACT_MISH, "act_grad_dropout: unknown activation");
-  int P;
-  if (int rc = op_form("act_grad_dropout", y, ldy, dtype, N, &P)) return rc;
-  ProfScope ps(st, PROF_OTHER, 0.0);
-  hipLaunchKernelGGL(act_op_drop_kernel<1>, dim3(op_grid(rows * (P / 8))), dim3(256), 0, st, z, ldz,
-                     ga, ldga, rows, N, act, static_cast<bf16_t*>(y), ldy, P,
-                     dtype == VTD_BF16X3 ? 1 : 0, dk);
-  VTD_LAUNCH_CHECK("act_grad_dropout");
   return VTD_OK;
 }
 
@@ -1404,9 +1385,8 @@ int vtd_act_forward_dropout(const float* z_dev, int64_t rows, int N, int ldz, in
   vtd::DropKey dk;
   bool on;
   if (int rc = vtd::drop_prepare("vtd_act_forward_dropout", drop, &dk, &on)) return rc;
-  if (!on) return vtd_act_forward(z_dev, rows, N, ldz, act, a_dev, lda, dtype, stream);
-  return vtd::act_forward_drop_launch(z_dev, rows, N, ldz, act, a_dev, lda, dtype, dk,
-                                      static_cast<hipStream_t>(stream));
+  return vtd::act_forward_launch(z_dev, rows, N, ldz, act, a_dev, lda, dtype,
+                                 static_cast<hipStream_t>(stream), on ? &dk : nullptr);
 }
 
 int vtd_act_grad_dropout(const float* z_dev, int ldz, const float* ga_dev, int ldga, int64_t rows,
@@ -1415,10 +1395,8 @@ int vtd_act_grad_dropout(const float* z_dev, int ldz, const float* ga_dev, int l
   vtd::DropKey dk;
   bool on;
   if (int rc = vtd::drop_prepare("vtd_act_grad_dropout", drop, &dk, &on)) return rc;
-  if (!on)
-    return vtd_act_grad(z_dev, ldz, ga_dev, ldga, rows, N, act, gz_dev, ldgz, dtype, stream);
-  return vtd::act_grad_drop_launch(z_dev, ldz, ga_dev, ldga, rows, N, act, gz_dev, ldgz, dtype, dk,
-                                   static_cast<hipStream_t>(stream));
+  return vtd::act_grad_launch(z_dev, ldz, ga_dev, ldga, rows, N, act, gz_dev, ldgz, dtype,
+                              static_cast<hipStream_t>(stream), on ? &dk : nullptr);
 }
 
 int vtd_dropout_apply(const vtd_dropout* drop, const float* x_dev, int ldx, int64_t rows, int N,

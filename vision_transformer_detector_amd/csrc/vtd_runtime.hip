@@ -1,6 +1,7 @@
 // Host runtime of libvtd.so: error state, graph shapes, workspace plan, the whole
 // forward (`model(images, training=False)`, vtd.py:498-583) as one sequence of
-// launches on the caller's stream, and optional hipEvent per-launch profiling.
+// launches on the caller's stream, and optional hipEvent per-launch profiling.  The training
+// chains are vtd_train_runtime.hip's.
 #include <atomic>
 #include <algorithm>
 #include <cmath>
@@ -108,7 +109,7 @@ ProfScope::~ProfScope() {
 }
 
 // ------------------------------------------------------------------ shapes
-static int derive(const vtd_config* c, vtd_dims* d) {
+int derive(const vtd_config* c, vtd_dims* d) {
   VTD_CHECK_ARG(c && d, "null config/dims");
   VTD_CHECK_ARG(c->batch > 0 && c->image_h > 0 && c->image_w > 0 && c->channels > 0,
                 "batch and input_shape must be positive");
@@ -133,15 +134,14 @@ static int derive(const vtd_config* c, vtd_dims* d) {
   d->patch_dim_p = (int)round_up(d->patch_dim, VTD_KALIGN);
   d->d = c->embedding_dim;
   d->d_p = (int)round_up(d->d, VTD_KALIGN);
-  int dkp = c->key_dim <= 32 ? 32 : (c->key_dim <= 64 ? 64 : 128);
-  if ((c->num_heads * dkp) % VTD_KALIGN) dkp *= 2;
+  const int dkp = key_dim_pad(c->num_heads, c->key_dim);
   VTD_CHECK_ARG(dkp <= 128, "key_dim padding exceeds 128");
   d->key_dim_p = dkp;
   d->inner_p = c->num_heads * dkp;
   d->qkv_p = (int)round_up(3 * d->inner_p, VTD_KALIGN);
   for (int j = 0; j < VTD_MAX_MLP; ++j) d->mlp_units[j] = d->mlp_units_p[j] = 0;
-  for (int j = 0; j < c->mlp_quantities; ++j) {      // vtd.py:385-386
-    const int64_t u = (int64_t)d->d << (c->mlp_quantities - 1 - j);
+  for (int j = 0; j < c->mlp_quantities; ++j) {
+    const int64_t u = mlp_width(d->d, c->mlp_quantities, j);
     VTD_CHECK_ARG(u < (1 << 24), "encoder MLP width overflow");
     d->mlp_units[j] = (int)u;
     d->mlp_units_p[j] = (int)round_up(u, VTD_KALIGN);
@@ -209,26 +209,8 @@ const Switches& switches() {
   }();
   return sw;
 }
-// What a vtd_config.dtype means for the forward's buffers and GEMMs.
-struct Mode {
-  // activation / non-MX matrix dtype (VTD_FP8 keeps everything else in bf16; the split-bf16
-  // mode VTD_BF16X3 keeps its activations -- query/key/value, attention -- in f32)
-  int act;
-  // GEMM operand dtype.  VTD_BF16X3: every GEMM runs on split-bf16 operands (bf16 kernels over
-  // K' = 3 K_p, A rows stored [hi | lo], 2 K_p wide), which the producers write directly
-  int op;
-  // dtype of the residual stream x: bf16 in the bf16 / fp8 modes (the stream the GEMM
-  // epilogues add into and the LayerNorms read), f32 in the f32 mode.  VTD_RESID_F32=1
-  // keeps an f32 stream in the bf16 modes (A/B diagnostic; costs ~7 % at C2).
-  int resid;
-  // bytes per element of an activation (es) and per logical element of a GEMM A operand --
-  // patches, LayerNorm out, MLP / head activations (eop; VTD_BF16X3: the pieces [hi | lo])
-  size_t es, eop;
-  bool fp8, x3;
-  // stored width of a K-wide logical A row, and the GEMM's K (the weights' row width) for it
-  int ka(int k) const { return x3 ? 2 * k : k; }
-  int kk(int k) const { return x3 ? 3 * k : k; }
-};
+}  // namespace
+// Mode (vtd_launch.h) of a vtd_config.dtype; the training chains call it too
 Mode mode_of(int dtype) {
   Mode m{};
   m.fp8 = dtype == VTD_FP8;
@@ -240,6 +222,7 @@ Mode mode_of(int dtype) {
   m.eop = m.x3 ? 4 : m.es;
   return m;
 }
+namespace {
 // Workspace offsets of one part, and the split-K counts its buffers were sized for: the
 // forward launches with exactly these (1 = no split).
 struct Plan {
@@ -299,32 +282,27 @@ int enc_splitk_choice(int64_t M, int N, int K, int nparts, int dtype, size_t max
 }
 Plan make_plan(const vtd_config* c, const vtd_dims& d, const Mode& m, int nparts = 1) {
   Plan p{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
-  };
+  Arena ar;
   const size_t es = m.es, eop = m.eop;
   const size_t R = (size_t)gemm_rows(d, nparts), HR = (size_t)d.head_rows;
   int mlp_max = 0, head_max = 0;
   for (int j = 0; j < c->mlp_quantities; ++j) mlp_max = std::max(mlp_max, d.mlp_units_p[j]);
   for (int j = 0; j < d.n_head; ++j) head_max = std::max(head_max, d.head_units_p[j]);
-  p.patches = take(R * d.patch_dim_p * eop);
-  p.x = take(R * d.d_p * 4);
-  p.xb = take(m.act == VTD_BF16 ? R * d.d_p * 2 : 0);
-  p.h = take(R * d.d_p * eop);
-  p.stat = take(R * 8);                 // LayerNorm (mean, rstd) per row, fold path
-  p.pstat = take(R * (d.d_p / 64) * 8);  // producer partial (sum, sumsq) per 64 columns
-  p.qkv = take(R * d.qkv_p * es);
+  p.patches = ar.take(R * d.patch_dim_p * eop);
+  p.x = ar.take(R * d.d_p * 4);
+  p.xb = ar.take(m.act == VTD_BF16 ? R * d.d_p * 2 : 0);
+  p.h = ar.take(R * d.d_p * eop);
+  p.stat = ar.take(R * 8);                 // LayerNorm (mean, rstd) per row, fold path
+  p.pstat = ar.take(R * (d.d_p / 64) * 8);  // producer partial (sum, sumsq) per 64 columns
+  p.qkv = ar.take(R * d.qkv_p * es);
   // the attention output; VTD_BF16X3: written by the attention kernel as the split-bf16
   // operand of attention_output, no f32 copy
-  p.attn = take(R * d.inner_p * (m.x3 ? eop : es));
-  p.mlp0 = take(R * mlp_max * eop);
-  p.mlp1 = take(R * mlp_max * eop);
-  p.u = take(HR * d.tokens_p * eop);
-  p.head0 = take(HR * head_max * eop);
-  p.head1 = take(HR * head_max * eop);
+  p.attn = ar.take(R * d.inner_p * (m.x3 ? eop : es));
+  p.mlp0 = ar.take(R * mlp_max * eop);
+  p.mlp1 = ar.take(R * mlp_max * eop);
+  p.u = ar.take(HR * d.tokens_p * eop);
+  p.head0 = ar.take(HR * head_max * eop);
+  p.head1 = ar.take(HR * head_max * eop);
   // fp32 split-K partials of the head's few-tile, long-K Dense layers (gemm_splitk_choice)
   size_t sk = 0;
   for (int j = 0, k = d.tokens_p; j < d.n_head; k = d.head_units_p[j], ++j) {
@@ -337,7 +315,7 @@ Plan make_plan(const vtd_config* c, const vtd_dims& d, const Mode& m, int nparts
   const bool enc = !m.fp8 && m.op != VTD_F32;
   if (enc) sk = std::max(sk, kEncSplitBytes);
   p.splitk_bytes = sk;
-  p.splitk = take(sk);
+  p.splitk = ar.take(sk);
   auto enc_ks = [&](int N, int K) {
     return enc && switches().enc_splitk
                ? enc_splitk_choice((int64_t)R, N, m.kk(K), nparts, m.op, p.splitk_bytes) : 1;
@@ -354,11 +332,11 @@ Plan make_plan(const vtd_config* c, const vtd_dims& d, const Mode& m, int nparts
     for (int j = 0; j + 1 < c->mlp_quantities; ++j) p.k8_max = std::max(p.k8_max, k8_of(d.mlp_units_p[j]));
   }
   // two MX-fp8 operand buffers: an MLP GEMM reads one and writes the next one's operand
-  p.q8 = take(R * p.k8_max);
-  p.s8 = take((size_t)p.s8_rows * p.k8_max / 32);
-  p.q8b = take(R * p.k8_max);
-  p.s8b = take((size_t)p.s8_rows * p.k8_max / 32);
-  p.total = off;
+  p.q8 = ar.take(R * p.k8_max);
+  p.s8 = ar.take((size_t)p.s8_rows * p.k8_max / 32);
+  p.q8b = ar.take(R * p.k8_max);
+  p.s8b = ar.take((size_t)p.s8_rows * p.k8_max / 32);
+  p.total = ar.off;
   return p;
 }
 // Two-stream micro-batching of vtd_forward: the images are independent, so a large
@@ -843,645 +821,6 @@ static int run_forward(const vtd_config* cfg, const vtd_weights* w, const float*
 }
 
 
-// ------------------------------------------------------------------ head backward
-// Workspace of vtd_head_backward: buffers in use order, 256-B aligned.  The converted weights
-// (wt: W^T for a forward GEMM, wkn: the Keras [K][N] form for an input-gradient GEMM) are one
-// buffer each, sized for the largest layer and reused layer by
-// layer -- the call runs on one stream, so the order of the launches is the order of use.
-namespace {
-struct HeadPlan {
-  size_t a_enc, u, z[VTD_MAX_HEAD], a[VTD_MAX_HEAD], logits, gf, gz, da[2], dt, wt, wkn, bias,
-      part, part_bytes, total;
-  int fwd_ks[VTD_MAX_HEAD];       // split-K of the forward GEMM of head layer j
-  int bwd_ks[VTD_MAX_HEAD + 1];   // of the input-gradient GEMM of layer j (n_head: the final one)
-  int wg_ms[VTD_MAX_HEAD + 2];    // msplit of the weight gradient: j, n_head = final, n_head + 1 = dense
-};
-HeadPlan head_plan(const vtd_dims& d, const Mode& m) {
-  HeadPlan p{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
-  };
-  const size_t R = (size_t)d.rows, HR = (size_t)d.head_rows, eop = m.eop;
-  const int nh = d.n_head, op = m.op;
-  size_t wmax = (size_t)64 * d.d_p, umax = std::max(d.tokens_p, 64), part = 0;
-  p.a_enc = take(R * d.d_p * eop);
-  p.u = take(HR * d.tokens_p * eop);
-  for (int j = 0, k = d.tokens_p, kv = d.tokens; j < nh; k = d.head_units_p[j], kv = d.head_units[j], ++j) {
-    const int up = d.head_units_p[j];
-    p.z[j] = take(HR * up * 4);
-    p.a[j] = take(HR * up * eop);
-    wmax = std::max(wmax, (size_t)up * k);
-    umax = std::max<size_t>(umax, up);
-    p.fwd_ks[j] = gemm_splitk_choice((int)HR, up, m.kk(k), op);
-    p.bwd_ks[j] = gemm_splitk_choice((int)HR, k, m.kk(up), op);
-    p.wg_ms[j] = gemm_wgrad_choice((int)HR, kv, d.head_units[j], op);
-    part = std::max(part, (size_t)p.fwd_ks[j] * HR * up * 4);
-    part = std::max(part, (size_t)p.bwd_ks[j] * HR * k * 4);
-    if (p.wg_ms[j] > 1) part = std::max(part, (size_t)p.wg_ms[j] * (kv + 1) * d.head_units[j] * 4);
-  }
-  const int kl = nh ? d.head_units_p[nh - 1] : d.tokens_p, klv = nh ? d.head_units[nh - 1] : d.tokens;
-  wmax = std::max(wmax, (size_t)64 * kl);
-  p.bwd_ks[nh] = gemm_splitk_choice((int)HR, kl, m.kk(64), op);
-  p.wg_ms[nh] = gemm_wgrad_choice((int)HR, klv, 6, op);
-  p.wg_ms[nh + 1] = gemm_wgrad_choice((int)R, d.d, VTD_MAX_DETECT, op);
-  part = std::max(part, (size_t)p.bwd_ks[nh] * HR * kl * 4);
-  if (p.wg_ms[nh] > 1) part = std::max(part, (size_t)p.wg_ms[nh] * (klv + 1) * 6 * 4);
-  if (p.wg_ms[nh + 1] > 1)
-    part = std::max(part, (size_t)p.wg_ms[nh + 1] * (d.d + 1) * VTD_MAX_DETECT * 4);
-  p.logits = take(HR * 6 * 4);
-  p.gf = take(HR * 64 * eop);
-  p.gz = take(HR * umax * eop);
-  p.da[0] = take(HR * umax * 4);
-  p.da[1] = take(HR * umax * 4);
-  p.dt = take(R * 64 * eop);
-  p.wt = take(wmax * (m.x3 ? 6 : 2));
-  p.wkn = take(wmax * (m.x3 ? 6 : 2));
-  p.bias = take(umax * 4);
-  p.part_bytes = part;
-  p.part = take(part);
-  p.total = off;
-  return p;
-}
-int head_mode(const vtd_config* cfg, vtd_dims* d, const char* what) {
-  if (int rc = derive(cfg, d)) return rc;
-  if (cfg->dtype != VTD_BF16X3 && cfg->dtype != VTD_BF16)
-    return fail(VTD_ERR_UNSUPPORTED, std::string(what) + ": cfg->dtype must be VTD_BF16X3 or "
-                                     "VTD_BF16 (VTD_F32 and VTD_FP8 have no backward)");
-  VTD_CHECK_ARG(d->rows < (int64_t)1 << 31, std::string(what) + ": batch*tokens too large");
-  return VTD_OK;
-}
-}  // namespace
-
-static int head_backward(const vtd_config* cfg, const vtd_head_params* w, const float* encoded,
-                         const float* dlogits, float* logits_out, const vtd_head_grads* g,
-                         void* ws_, size_t ws_bytes, void* stream_,
-                         const vtd_block_dropout* drop = nullptr) {
-  vtd_dims d;
-  if (int rc = head_mode(cfg, &d, "head_backward")) return rc;
-  // dropout (optional): site_base + j follows head layer j's activation, over the unpadded
-  // [B 17][units_j] plane.  The backward's recomputed forward regenerates the forward's masks
-  DropKey dk_head[VTD_MAX_HEAD]{};
-  bool drop_on = false;
-  if (drop) {
-    VTD_CHECK_ARG((uint64_t)drop->site_base + d.n_head <= 0xffffffffull,
-                  "head_backward_dropout: site_base + n_head overflows 32 bits");
-    for (int j = 0; j < d.n_head; ++j) {
-      const vtd_dropout dj{drop->seed, drop->step, drop->site_base + (uint32_t)j, drop->rate};
-      if (int rc = drop_prepare("head_backward_dropout", &dj, &dk_head[j], &drop_on)) return rc;
-    }
-  }
-  VTD_CHECK_ARG(w && encoded && ws_ && (dlogits ? g != nullptr : logits_out != nullptr),
-                "head_backward: null pointer");
-  const int nh = d.n_head;
-  VTD_CHECK_ARG(w->w_det && w->b_det && w->w_final && w->b_final,
-                "head_backward: null weight pointer");
-  for (int j = 0; j < nh; ++j)
-    VTD_CHECK_ARG(w->w_head[j] && w->b_head[j], "head_backward: null weight pointer");
-  if (dlogits) {
-    VTD_CHECK_ARG(g->w_det && g->b_det && g->w_final && g->b_final,
-                  "head_backward: null gradient pointer");
-    for (int j = 0; j < nh; ++j)
-      VTD_CHECK_ARG(g->w_head[j] && g->b_head[j], "head_backward: null gradient pointer");
-  }
-  const Mode m = mode_of(cfg->dtype);
-  const HeadPlan P = head_plan(d, m);
-  if (ws_bytes < P.total)
-    return fail(VTD_ERR_WORKSPACE, "head_backward: workspace too small (need " +
-                                       std::to_string(P.total) + " bytes)");
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(ws_);
-  const int op = m.op, R = (int)d.rows, HR = (int)d.head_rows, T = d.tokens, Tp = d.tokens_p;
-  const int D = d.d, Dp = d.d_p, act = cfg->use_mish ? VTD_ACT_MISH : VTD_ACT_GELU_TANH;
-  float* part = reinterpret_cast<float*>(ws + P.part);
-  float* bias = reinterpret_cast<float*>(ws + P.bias);
-  float* logits = logits_out ? logits_out : reinterpret_cast<float*>(ws + P.logits);
-  int rc;
-  // Keras kernel [K][N] -> W^T [Np][kk(Kp)] in the operand dtype (the forward GEMMs' Bt), pad
-  // rows and columns zero
-  auto conv_t = [&](const float* src, int K, int N, int Kp, int Np) -> int {
-    return transpose_op_launch(src, K, N, ws + P.wt, Kp, Np, op, st);
-  };
-  // Keras kernel [K][N] -> [Kp][kk(Np)] in the operand dtype (Bt of dA = dZ W^T): the rows as
-  // stored, pad rows and columns zero
-  auto conv_kn = [&](const float* src, int K, int N, int Kp, int Np) -> int {
-    void* dst = ws + P.wkn;
-    VTD_HIP(hipMemsetAsync(dst, 0, (size_t)Kp * m.kk(Np) * 2, st));
-    return m.x3 ? split_bf16x3_launch(src, K, N, N, dst, 3 * Np, 1, st)
-                : act_forward_launch(src, K, N, N, VTD_ACT_NONE, dst, Np, VTD_BF16, st);
-  };
-  auto pad_bias = [&](const float* b, int N, int Np) -> int {
-    VTD_HIP(hipMemsetAsync(bias, 0, (size_t)Np * 4, st));
-    VTD_HIP(hipMemcpyAsync(bias, b, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-    return VTD_OK;
-  };
-  auto gemm = [&](int M, int N, int K, const void* A, int lda, const void* Bt, int ks,
-                  const vtd_epilogue& e, double fl) -> int {
-    return ks > 1 ? gemm_splitk_launch(M, N, K, A, lda, Bt, K, op, &e, part, ks, st, fl)
-                  : gemm_launch(M, N, K, A, lda, Bt, K, op, &e, st, fl);
-  };
-  auto wgrad = [&](int M, int K, int N, const void* X, int ldx, const void* G, int ldg, float* dW,
-                   float* db, int ms) -> int {
-    return gemm_wgrad_launch(M, K, N, X, ldx, G, ldg, op, dW, N, db, part, P.part_bytes, ms, st);
-  };
-
-  // ================= training forward from `encoded`: z and the activations are kept
-  void* a_enc = ws + P.a_enc;
-  void* u = ws + P.u;
-  if ((rc = act_forward_launch(encoded, R, D, D, VTD_ACT_NONE, a_enc, m.ka(Dp), op, st))) return rc;
-  {                                   // Dense(17) + Reshape as the scatter epilogue
-    if ((rc = conv_t(w->w_det, D, VTD_MAX_DETECT, Dp, 64))) return rc;
-    if ((rc = pad_bias(w->b_det, VTD_MAX_DETECT, 64))) return rc;
-    VTD_HIP(hipMemsetAsync(u, 0, (size_t)HR * Tp * m.eop, st));
-    vtd_epilogue e{};
-    e.bias = bias; e.act = VTD_ACT_NONE;
-    e.out = u; e.ldo = m.ka(Tp); e.out_dtype = op;
-    e.scatter_tokens = T;
-    if ((rc = gemm_launch(R, VTD_MAX_DETECT, m.kk(Dp), a_enc, m.ka(Dp), ws + P.wt, m.kk(Dp), op,
-                          &e, st, 2.0 * R * D * VTD_MAX_DETECT)))
-      return rc;
-  }
-  const void* a = u;
-  int k = Tp, kv = T;
-  for (int j = 0; j < nh; ++j) {
-    const int up = d.head_units_p[j], uv = d.head_units[j];
-    if ((rc = conv_t(w->w_head[j], kv, uv, k, up))) return rc;
-    if ((rc = pad_bias(w->b_head[j], uv, up))) return rc;
-    vtd_epilogue e{};
-    e.bias = bias; e.act = VTD_ACT_NONE;
-    e.out = ws + P.z[j]; e.ldo = up; e.out_dtype = VTD_F32;
-    if ((rc = gemm(HR, up, m.kk(k), a, m.ka(k), ws + P.wt, P.fwd_ks[j], e, 2.0 * HR * kv * uv)))
-      return rc;
-    const float* z = reinterpret_cast<const float*>(ws + P.z[j]);
-    if ((rc = drop_on ? act_forward_drop_launch(z, HR, uv, up, act, ws + P.a[j], m.ka(up), op,
-                                                dk_head[j], st)
-                      : act_forward_launch(z, HR, uv, up, act, ws + P.a[j], m.ka(up), op, st)))
-      return rc;
-    a = ws + P.a[j];
-    k = up; kv = uv;
-  }
-  {                                   // MLP_Head_no_Sigmoid
-    if ((rc = conv_t(w->w_final, kv, 6, k, 64))) return rc;
-    if ((rc = pad_bias(w->b_final, 6, 64))) return rc;
-    vtd_epilogue e{};
-    e.bias = bias; e.act = VTD_ACT_NONE;
-    e.out = logits; e.ldo = 6; e.out_dtype = VTD_F32;
-    if ((rc = gemm_launch(HR, 6, m.kk(k), a, m.ka(k), ws + P.wt, m.kk(k), op, &e, st,
-                          2.0 * HR * kv * 6)))
-      return rc;
-  }
-
-  if (!dlogits) return VTD_OK;         // the training forward alone (logits_out)
-
-  // ================= backward
-  void* gf = ws + P.gf;
-  void* gz = ws + P.gz;
-  float* da[2] = {reinterpret_cast<float*>(ws + P.da[0]), reinterpret_cast<float*>(ws + P.da[1])};
-  if ((rc = act_forward_launch(dlogits, HR, 6, 6, VTD_ACT_NONE, gf, m.ka(64), op, st))) return rc;
-  if ((rc = wgrad(HR, kv, 6, a, m.ka(k), gf, m.ka(64), g->w_final, g->b_final, P.wg_ms[nh])))
-    return rc;
-  int cur = 0;                        // da[cur] = d loss / d (the activation feeding the layer above)
-  {
-    if ((rc = conv_kn(w->w_final, kv, 6, k, 64))) return rc;
-    vtd_epilogue e{};
-    e.act = VTD_ACT_NONE;
-    e.out = da[cur]; e.ldo = k; e.out_dtype = VTD_F32;
-    if ((rc = gemm(HR, k, m.kk(64), gf, m.ka(64), ws + P.wkn, P.bwd_ks[nh], e, 2.0 * HR * kv * 6)))
-      return rc;
-  }
-  for (int j = nh - 1; j >= 0; --j) {
-    const int up = d.head_units_p[j], uv = d.head_units[j];
-    const int kin = j ? d.head_units_p[j - 1] : Tp, kinv = j ? d.head_units[j - 1] : T;
-    const void* ain = j ? ws + P.a[j - 1] : u;
-    const float* z = reinterpret_cast<const float*>(ws + P.z[j]);
-    if ((rc = drop_on ? act_grad_drop_launch(z, up, da[cur], up, HR, uv, act, gz, m.ka(up), op,
-                                             dk_head[j], st)
-                      : act_grad_launch(z, up, da[cur], up, HR, uv, act, gz, m.ka(up), op, st)))
-      return rc;
-    if ((rc = wgrad(HR, kinv, uv, ain, m.ka(kin), gz, m.ka(up), g->w_head[j], g->b_head[j],
-                    P.wg_ms[j])))
-      return rc;
-    if ((rc = conv_kn(w->w_head[j], kinv, uv, kin, up))) return rc;
-    vtd_epilogue e{};
-    e.act = VTD_ACT_NONE;
-    e.out = da[cur ^ 1]; e.ldo = kin; e.out_dtype = VTD_F32;
-    if ((rc = gemm(HR, kin, m.kk(up), gz, m.ka(up), ws + P.wkn, P.bwd_ks[j], e,
-                   2.0 * HR * kinv * uv)))
-      return rc;
-    cur ^= 1;
-  }
-  // da[cur] = dU [B 17][Tp]: back through the Reshape, then Dense(17)
-  void* dt = ws + P.dt;
-  if ((rc = head_unscatter_launch(da[cur], cfg->batch, T, Tp, dt, m.ka(64), op, st))) return rc;
-  if ((rc = wgrad(R, D, VTD_MAX_DETECT, a_enc, m.ka(Dp), dt, m.ka(64), g->w_det, g->b_det,
-                  P.wg_ms[nh + 1])))
-    return rc;
-  if (g->d_encoded) {
-    if ((rc = conv_kn(w->w_det, D, VTD_MAX_DETECT, Dp, 64))) return rc;
-    vtd_epilogue e{};
-    e.act = VTD_ACT_NONE;
-    e.out = g->d_encoded; e.ldo = D; e.out_dtype = VTD_F32;
-    if ((rc = gemm_launch(R, D, m.kk(64), dt, m.ka(64), ws + P.wkn, m.kk(64), op, &e, st,
-                          2.0 * R * D * VTD_MAX_DETECT)))
-      return rc;
-  }
-  return VTD_OK;
-}
-
-// ------------------------------------------------------------------ encoder block backward
-// One encoder block (vtd.py:350-412, dropout=None) built as vtd_head_backward is: a training
-// forward that keeps what the backward needs, then the backward; one stream, a caller workspace.
-namespace {
-struct BlockShape {
-  int64_t rows;
-  int B, T, D, Dp, H, kd, dkp, inner, inner_p, qkv_p, q;
-  int u[VTD_MAX_MLP], up[VTD_MAX_MLP];
-};
-int block_shape(const vtd_block_dims* c, BlockShape* s, const char* what) {
-  const std::string w(what);
-  VTD_CHECK_ARG(c, w + ": null dims");
-  VTD_CHECK_ARG(c->batch > 0 && c->tokens > 0 && c->d > 0 && c->num_heads > 0 && c->key_dim > 0 &&
-                    c->mlp_quantities > 0,
-                w + ": batch, tokens, d, num_heads, key_dim, mlp_quantities must be > 0");
-  VTD_CHECK_ARG(c->mlp_quantities <= VTD_MAX_MLP, w + ": mlp_quantities too large");
-  VTD_CHECK_ARG(c->key_dim <= 128, w + ": key_dim > 128 not supported");
-  if (c->dtype != VTD_BF16X3 && c->dtype != VTD_BF16)
-    return fail(VTD_ERR_UNSUPPORTED, w + ": dims->dtype must be VTD_BF16X3 or VTD_BF16 (VTD_F32 "
-                                         "and VTD_FP8 have no backward)");
-  s->rows = (int64_t)c->batch * c->tokens;
-  VTD_CHECK_ARG(s->rows < (int64_t)1 << 31, w + ": batch*tokens too large");
-  s->B = c->batch; s->T = c->tokens; s->D = c->d; s->H = c->num_heads; s->kd = c->key_dim;
-  s->q = c->mlp_quantities;
-  VTD_CHECK_ARG(c->d < (1 << 24) && (int64_t)c->num_heads * 128 * 3 < (1 << 24),
-                w + ": d or num_heads too large");
-  s->Dp = (int)round_up(s->D, VTD_KALIGN);
-  int dkp = s->kd <= 32 ? 32 : (s->kd <= 64 ? 64 : 128);      // as derive()
-  if ((s->H * dkp) % VTD_KALIGN) dkp *= 2;
-  VTD_CHECK_ARG(dkp <= 128, w + ": key_dim padding exceeds 128");
-  s->dkp = dkp;
-  s->inner = s->H * s->kd;
-  s->inner_p = s->H * dkp;
-  s->qkv_p = (int)round_up(3 * s->inner_p, VTD_KALIGN);
-  for (int j = 0; j < VTD_MAX_MLP; ++j) s->u[j] = s->up[j] = 0;
-  for (int j = 0; j < s->q; ++j) {                            // vtd.py:385-386
-    const int64_t u = (int64_t)s->D << (s->q - 1 - j);
-    VTD_CHECK_ARG(u < (1 << 24), w + ": MLP width overflow");
-    s->u[j] = (int)u;
-    s->up[j] = (int)round_up(u, VTD_KALIGN);
-  }
-  return VTD_OK;
-}
-// Workspace of vtd_encoder_block_backward: buffers in use order, 256-B aligned.  wt / wkn / bias:
-// one converted-weight buffer each, sized for the largest layer and reused layer by layer (one
-// stream: the order of the launches is the order of use); `part`: the split-K / msplit partials,
-// sized for the largest use; ln / att: the LayerNorm and attention backward workspaces.
-struct BlockPlan {
-  size_t stat1, h1, wt, bias, qkv, attn, lse, x1, stat2, h2, z[VTD_MAX_MLP], a[VTD_MAX_MLP], gz,
-      da[2], wkn, dx1, gop, dO, dqkv, dwqkv, dbqkv, dwo, ln, ln_bytes, att, att_bytes, part,
-      part_bytes, total;
-  int f_qkv, f_out, f_mlp[VTD_MAX_MLP];      // split-K of the forward GEMMs
-  int b_mlp[VTD_MAX_MLP], b_out, b_qkv;      // of the input-gradient GEMMs
-  int wg_mlp[VTD_MAX_MLP], wg_out, wg_qkv;   // msplit of the weight gradients
-};
-int block_plan(const BlockShape& s, const Mode& m, int dtype, BlockPlan* out) {
-  BlockPlan p{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
-  };
-  const size_t R = (size_t)s.rows, eop = m.eop, es = m.es;
-  const int op = m.op, M = (int)s.rows;
-  size_t part = 0;
-  // split-K needs N % 4 == 0 (its reduce pass reads 16-B vectors).  The count falls back to 1
-  // once the rows fill the chip, so the partials are reserved by a bound that only grows with
-  // the rows and the workspace stays monotonic in the batch: gemm_splitk_choice gives at most
-  // K / 64 / 8 splits, and only below 192 tiles of 256 x 256 with splits x tiles < 448.
-  auto ks_of = [&](int N, int K) {
-    if (N % 4 != 0) return 1;
-    const int ks = gemm_splitk_choice(M, N, K, op);
-    const size_t smax = (size_t)(K / 64 / 8);
-    if (N > 64 && smax >= 2)
-      part = std::max(part, std::min(smax * R * N * 4, (size_t)448 * 256 * 256 * 4));
-    if (ks > 1) part = std::max(part, (size_t)ks * R * N * 4);
-    return ks;
-  };
-  auto ms_of = [&](int K, int N) {
-    const int ms = gemm_wgrad_choice(M, K, N, op);
-    if (ms > 1) part = std::max(part, (size_t)ms * (K + 1) * N * 4);
-    return ms;
-  };
-  size_t wmax = std::max((size_t)s.qkv_p * s.Dp, (size_t)s.Dp * s.inner_p);
-  size_t umax = std::max(s.Dp, s.qkv_p);
-  for (int j = 0, k = s.Dp; j < s.q; k = s.up[j], ++j) {
-    wmax = std::max(wmax, (size_t)s.up[j] * k);
-    umax = std::max<size_t>(umax, s.up[j]);
-  }
-  p.stat1 = take(R * 8);
-  p.h1 = take(R * s.Dp * eop);
-  p.wt = take(wmax * (m.x3 ? 6 : 2));
-  p.bias = take(umax * 4);
-  p.qkv = take(R * s.qkv_p * es);
-  p.attn = take(R * s.inner_p * eop);
-  p.lse = take((size_t)s.B * s.H * s.T * 4);
-  p.x1 = take(R * s.D * 4);
-  p.stat2 = take(R * 8);
-  p.h2 = take(R * s.Dp * eop);
-  p.f_qkv = ks_of(s.qkv_p, m.kk(s.Dp));
-  p.f_out = ks_of(s.D, m.kk(s.inner_p));
-  for (int j = 0, k = s.Dp, kv = s.D; j < s.q; k = s.up[j], kv = s.u[j], ++j) {
-    p.z[j] = take(R * s.up[j] * 4);
-    p.a[j] = take(j + 1 < s.q ? R * s.up[j] * eop : 0);
-    p.f_mlp[j] = ks_of(s.up[j], m.kk(k));
-    p.b_mlp[j] = ks_of(j ? k : s.D, m.kk(s.up[j]));
-    p.wg_mlp[j] = ms_of(kv, s.u[j]);
-  }
-  p.b_out = ks_of(s.inner_p, m.kk(s.Dp));
-  p.b_qkv = ks_of(s.D, m.kk(s.qkv_p));
-  p.wg_out = ms_of(s.inner_p, s.D);
-  p.wg_qkv = ms_of(s.D, s.qkv_p);
-  p.gz = take(R * umax * eop);
-  p.da[0] = take(R * umax * 4);
-  p.da[1] = take(R * umax * 4);
-  p.wkn = take(wmax * (m.x3 ? 6 : 2));
-  p.dx1 = take(R * s.D * 4);
-  p.gop = take(R * s.Dp * eop);
-  p.dO = take(R * s.inner_p * es);
-  p.dqkv = take(R * s.qkv_p * eop);
-  p.dwqkv = take((size_t)s.D * s.qkv_p * 4);
-  p.dbqkv = take((size_t)s.qkv_p * 4);
-  p.dwo = take((size_t)s.inner_p * s.D * 4);
-  if (int rc = layernorm_backward_workspace_bytes(s.rows, s.D, &p.ln_bytes)) return rc;
-  p.ln = take(p.ln_bytes);
-  if (int rc = attention_backward_workspace_bytes(s.B, s.T, s.H, s.dkp, dtype, &p.att_bytes))
-    return rc;
-  p.att = take(p.att_bytes);
-  p.part_bytes = part;
-  p.part = take(part);
-  p.total = off;
-  *out = p;
-  return VTD_OK;
-}
-}  // namespace
-
-static int encoder_block_backward(const vtd_block_dims* c, const vtd_block_params* w,
-                                  const float* x, const float* dy, float* y,
-                                  const vtd_block_grads* g, void* ws_, size_t ws_bytes,
-                                  void* stream_, const vtd_block_dropout* drop = nullptr) {
-  BlockShape s;
-  if (int rc = block_shape(c, &s, "encoder_block_backward")) return rc;
-  // dropout (optional): site_base the attention probabilities, site_base + 1 + j MLP layer j.
-  // The backward's recomputed forward regenerates the forward's masks: the same (seed, step, site)
-  DropKey dk_att{}, dk_mlp[VTD_MAX_MLP]{};
-  bool drop_on = false;
-  if (drop) {
-    VTD_CHECK_ARG((uint64_t)drop->site_base + s.q <= 0xffffffffull,
-                  "encoder_block_backward_dropout: site_base + mlp_quantities overflows 32 bits");
-    for (int j = -1; j < s.q; ++j) {
-      const vtd_dropout d{drop->seed, drop->step, drop->site_base + (uint32_t)(1 + j), drop->rate};
-      if (int rc = drop_prepare("encoder_block_backward_dropout", &d, j < 0 ? &dk_att : &dk_mlp[j],
-                                &drop_on))
-        return rc;
-    }
-  }
-  VTD_CHECK_ARG(w && x && ws_ && (dy ? g != nullptr : y != nullptr),
-                "encoder_block_backward: null pointer");
-  VTD_CHECK_ARG(w->ln1_gamma && w->ln1_beta && w->wq && w->bq && w->wk && w->bk && w->wv && w->bv &&
-                    w->wo && w->bo && w->ln2_gamma && w->ln2_beta,
-                "encoder_block_backward: null weight pointer");
-  for (int j = 0; j < s.q; ++j)
-    VTD_CHECK_ARG(w->w_mlp[j] && w->b_mlp[j], "encoder_block_backward: null weight pointer");
-  if (dy) {
-    VTD_CHECK_ARG(g->ln1_gamma && g->ln1_beta && g->wq && g->bq && g->wk && g->bk && g->wv &&
-                      g->bv && g->wo && g->bo && g->ln2_gamma && g->ln2_beta,
-                  "encoder_block_backward: null gradient pointer");
-    for (int j = 0; j < s.q; ++j)
-      VTD_CHECK_ARG(g->w_mlp[j] && g->b_mlp[j], "encoder_block_backward: null gradient pointer");
-  }
-  const Mode m = mode_of(c->dtype);
-  BlockPlan P;
-  if (int rc = block_plan(s, m, c->dtype, &P)) return rc;
-  if (ws_bytes < P.total)
-    return fail(VTD_ERR_WORKSPACE, "encoder_block_backward: workspace too small (need " +
-                                       std::to_string(P.total) + " bytes)");
-  hipStream_t st = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(ws_);
-  const int op = m.op, R = (int)s.rows, D = s.D, Dp = s.Dp, q = s.q;
-  const int act = c->use_mish ? VTD_ACT_MISH : VTD_ACT_GELU_TANH;
-  const int adt = m.x3 ? VTD_F32 : VTD_BF16;     // what the attention kernels read: qkv, dO
-  const float scale = 1.0f / std::sqrt((float)s.kd);
-  auto f32p = [&](size_t o) { return reinterpret_cast<float*>(ws + o); };
-  float* part = f32p(P.part);
-  float* bias = f32p(P.bias);
-  float *stat1 = f32p(P.stat1), *stat2 = f32p(P.stat2), *x1 = f32p(P.x1), *lse = f32p(P.lse);
-  void *h1 = ws + P.h1, *h2 = ws + P.h2, *qkv = ws + P.qkv, *attn = ws + P.attn;
-  void *wt = ws + P.wt, *wkn = ws + P.wkn;
-  int rc;
-  auto conv_t = [&](const float* src, int K, int N, int Kp, int Np) -> int {
-    return transpose_op_launch(src, K, N, wt, Kp, Np, op, st);
-  };
-  auto conv_kn = [&](const float* src, int K, int N, int Kp, int Np) -> int {
-    VTD_HIP(hipMemsetAsync(wkn, 0, (size_t)Kp * m.kk(Np) * 2, st));
-    return m.x3 ? split_bf16x3_launch(src, K, N, N, wkn, 3 * Np, 1, st)
-                : act_forward_launch(src, K, N, N, VTD_ACT_NONE, wkn, Np, VTD_BF16, st);
-  };
-  auto pad_bias = [&](const float* b, int N, int Np) -> int {
-    VTD_HIP(hipMemsetAsync(bias, 0, (size_t)Np * 4, st));
-    VTD_HIP(hipMemcpyAsync(bias, b, (size_t)N * 4, hipMemcpyDeviceToDevice, st));
-    return VTD_OK;
-  };
-  auto gemm = [&](int N, int K, const void* A, int lda, const void* Bt, int ks,
-                  const vtd_epilogue& e, double fl) -> int {
-    return ks > 1 ? gemm_splitk_launch(R, N, K, A, lda, Bt, K, op, &e, part, ks, st, fl)
-                  : gemm_launch(R, N, K, A, lda, Bt, K, op, &e, st, fl);
-  };
-  auto wgrad = [&](int K, int N, const void* X, int ldx, const void* G, int ldg, float* dW,
-                   int ldw, float* db, int ms) -> int {
-    return gemm_wgrad_launch(R, K, N, X, ldx, G, ldg, op, dW, ldw, db, part, P.part_bytes, ms, st);
-  };
-  // the fused, per-head padded query/key/value matrix [Dp][qkv_p], its bias, and
-  // attention_output [inner_p][Dp] (BlockGather, vtd_launch.h)
-  const BlockGather gq{{w->wq, w->wk, w->wv}, 3, D, s.inner, D, Dp, s.kd, s.dkp, s.inner_p, Dp,
-                       s.qkv_p};
-  const BlockGather gqb{{w->bq, w->bk, w->bv}, 3, 1, s.inner, 1, 1, s.kd, s.dkp, s.inner_p, 1,
-                        s.qkv_p};
-  const BlockGather go{{w->wo, nullptr, nullptr}, 1, s.inner, D, s.kd, s.dkp, D, Dp, Dp, s.inner_p,
-                       Dp};
-
-  // ================= training forward: every pre-activation is kept
-  if ((rc = ln_stats_launch(x, VTD_F32, R, D, D, 1e-3f, stat1, st))) return rc;
-  if ((rc = layernorm_launch(x, VTD_F32, R, D, D, w->ln1_gamma, w->ln1_beta, 1e-3f, h1, m.ka(Dp),
-                             op, st)))
-    return rc;
-  {                                   // query / key / value, one fused GEMM
-    if ((rc = block_gather_launch(gq, wt, nullptr, op, st))) return rc;
-    if ((rc = block_gather_bias_launch(gqb, bias, st))) return rc;
-    vtd_epilogue e{};
-    e.bias = bias; e.act = VTD_ACT_NONE;
-    e.out = qkv; e.ldo = s.qkv_p; e.out_dtype = adt;
-    if ((rc = gemm(s.qkv_p, m.kk(Dp), h1, m.ka(Dp), wt, P.f_qkv, e, 2.0 * R * D * 3.0 * s.inner)))
-      return rc;
-  }
-  if ((rc = drop_on ? attention_train_drop_launch(qkv, s.B, s.T, s.H, s.dkp, s.qkv_p, scale, attn,
-                                                  m.ka(s.inner_p), lse, c->dtype, dk_att, st)
-                    : attention_train_launch(qkv, s.B, s.T, s.H, s.dkp, s.qkv_p, scale, attn,
-                                             m.ka(s.inner_p), lse, c->dtype, st)))
-    return rc;
-  {                                   // x1 = x + O Wo + bo
-    if ((rc = block_gather_launch(go, wt, nullptr, op, st))) return rc;
-    vtd_epilogue e{};
-    e.bias = w->bo; e.act = VTD_ACT_NONE;
-    e.resid = x; e.ldr = D;
-    e.out = x1; e.ldo = D; e.out_dtype = VTD_F32;
-    if ((rc = gemm(D, m.kk(s.inner_p), attn, m.ka(s.inner_p), wt, P.f_out, e,
-                   2.0 * R * s.inner * D)))
-      return rc;
-  }
-  if ((rc = ln_stats_launch(x1, VTD_F32, R, D, D, 1e-3f, stat2, st))) return rc;
-  if ((rc = layernorm_launch(x1, VTD_F32, R, D, D, w->ln2_gamma, w->ln2_beta, 1e-3f, h2, m.ka(Dp),
-                             op, st)))
-    return rc;
-  {
-    const void* a = h2;
-    for (int j = 0, k = Dp, kv = D; j < q; k = s.up[j], kv = s.u[j], ++j) {
-      const int up = s.up[j], uv = s.u[j];
-      if ((rc = conv_t(w->w_mlp[j], kv, uv, k, up))) return rc;
-      if ((rc = pad_bias(w->b_mlp[j], uv, up))) return rc;
-      vtd_epilogue e{};
-      e.bias = bias; e.act = VTD_ACT_NONE;
-      e.out = ws + P.z[j]; e.ldo = up; e.out_dtype = VTD_F32;
-      if ((rc = gemm(up, m.kk(k), a, m.ka(k), wt, P.f_mlp[j], e, 2.0 * R * kv * uv))) return rc;
-      if (j + 1 < q) {
-        if ((rc = drop_on ? act_forward_drop_launch(f32p(P.z[j]), R, uv, up, act, ws + P.a[j],
-                                                    m.ka(up), op, dk_mlp[j], st)
-                          : act_forward_launch(f32p(P.z[j]), R, uv, up, act, ws + P.a[j], m.ka(up),
-                                               op, st)))
-          return rc;
-        a = ws + P.a[j];
-      }
-    }
-  }
-  if (y && (rc = block_resid_act_launch(x1, D, f32p(P.z[q - 1]), s.up[q - 1], R, D, act, y, D, st,
-                                        drop_on ? &dk_mlp[q - 1] : nullptr)))
-    return rc;
-
-  if (!dy) return VTD_OK;              // the training forward alone (y_dev)
-
-  // ================= backward
-  void* gz = ws + P.gz;
-  float* da[2] = {f32p(P.da[0]), f32p(P.da[1])};
-  const float* gin = dy;               // d loss / d (the activation feeding the layer above)
-  int ldgin = D, cur = 0;
-  for (int j = q - 1; j >= 0; --j) {   // 1. the MLP
-    const int up = s.up[j], uv = s.u[j];
-    const int kin = j ? s.up[j - 1] : Dp, kinv = j ? s.u[j - 1] : D;
-    const void* ain = j ? ws + P.a[j - 1] : h2;
-    if ((rc = drop_on ? act_grad_drop_launch(f32p(P.z[j]), up, gin, ldgin, R, uv, act, gz, m.ka(up),
-                                             op, dk_mlp[j], st)
-                      : act_grad_launch(f32p(P.z[j]), up, gin, ldgin, R, uv, act, gz, m.ka(up), op,
-                                        st)))
-      return rc;
-    if ((rc = wgrad(kinv, uv, ain, m.ka(kin), gz, m.ka(up), g->w_mlp[j], uv, g->b_mlp[j],
-                    P.wg_mlp[j])))
-      return rc;
-    if ((rc = conv_kn(w->w_mlp[j], kinv, uv, kin, up))) return rc;
-    const int nout = j ? kin : D;      // the block's own width leaves unpadded: LayerNorm reads it
-    vtd_epilogue e{};
-    e.act = VTD_ACT_NONE;
-    e.out = da[cur]; e.ldo = nout; e.out_dtype = VTD_F32;
-    if ((rc = gemm(nout, m.kk(up), gz, m.ka(up), wkn, P.b_mlp[j], e, 2.0 * R * kinv * uv)))
-      return rc;
-    gin = da[cur]; ldgin = nout;
-    cur ^= 1;
-  }
-  // 2. LayerNorm 2; the residual's gradient dy joins as `add`
-  float* dx1 = f32p(P.dx1);
-  if ((rc = layernorm_backward_launch(x1, D, stat2, w->ln2_gamma, gin, D, dy, D, R, D, dx1, D,
-                                      g->ln2_gamma, g->ln2_beta, ws + P.ln, P.ln_bytes, st)))
-    return rc;
-  // 3. attention_output
-  void* gop = ws + P.gop;
-  void* dO = ws + P.dO;
-  if ((rc = act_forward_launch(dx1, R, D, D, VTD_ACT_NONE, gop, m.ka(Dp), op, st))) return rc;
-  if ((rc = wgrad(s.inner_p, D, attn, m.ka(s.inner_p), gop, m.ka(Dp), f32p(P.dwo), D, g->bo,
-                  P.wg_out)))
-    return rc;
-  {
-    float* const dst[1] = {g->wo};
-    if ((rc = block_ungather_launch(go, dst, nullptr, f32p(P.dwo), D, nullptr, st))) return rc;
-    if ((rc = block_gather_launch(go, nullptr, wkn, op, st))) return rc;
-    vtd_epilogue e{};                  // the pad rows of wkn are zero: so are dO's pad columns
-    e.act = VTD_ACT_NONE;
-    e.out = dO; e.ldo = s.inner_p; e.out_dtype = adt;
-    if ((rc = gemm(s.inner_p, m.kk(Dp), gop, m.ka(Dp), wkn, P.b_out, e, 2.0 * R * s.inner * D)))
-      return rc;
-  }
-  // 4. the attention core
-  void* dqkv = ws + P.dqkv;
-  if ((rc = attention_backward_launch(qkv, attn, dO, lse, s.B, s.T, s.H, s.dkp, s.qkv_p,
-                                      m.ka(s.inner_p), s.inner_p, scale, dqkv, m.ka(s.qkv_p),
-                                      c->dtype, ws + P.att, P.att_bytes, st,
-                                      drop_on ? &dk_att : nullptr)))
-    return rc;
-  // 5. query / key / value
-  if ((rc = wgrad(D, s.qkv_p, h1, m.ka(Dp), dqkv, m.ka(s.qkv_p), f32p(P.dwqkv), s.qkv_p,
-                  f32p(P.dbqkv), P.wg_qkv)))
-    return rc;
-  {
-    float* const dst[3] = {g->wq, g->wk, g->wv};
-    float* const dstb[3] = {g->bq, g->bk, g->bv};
-    if ((rc = block_ungather_launch(gq, dst, dstb, f32p(P.dwqkv), s.qkv_p, f32p(P.dbqkv), st)))
-      return rc;
-    if ((rc = block_gather_launch(gq, nullptr, wkn, op, st))) return rc;
-    vtd_epilogue e{};
-    e.act = VTD_ACT_NONE;
-    e.out = da[cur]; e.ldo = D; e.out_dtype = VTD_F32;
-    if ((rc = gemm(D, m.kk(s.qkv_p), dqkv, m.ka(s.qkv_p), wkn, P.b_qkv, e,
-                   2.0 * R * D * 3.0 * s.inner)))
-      return rc;
-  }
-  // 6. LayerNorm 1; dx1 joins along the residual.  Without a dx output the row pass still runs
-  // for dgamma / dbeta and writes in place over dx1
-  return layernorm_backward_launch(x, D, stat1, w->ln1_gamma, da[cur], D, dx1, D, R, D,
-                                   g->dx ? g->dx : dx1, D, g->ln1_gamma, g->ln1_beta, ws + P.ln,
-                                   P.ln_bytes, st);
-}
-
-extern "C" {
-
-int vtd_encoder_block_backward_workspace_bytes(const vtd_block_dims* dims, size_t* bytes) {
-  VTD_CHECK_ARG(bytes, "null bytes pointer");
-  BlockShape s;
-  if (int rc = block_shape(dims, &s, "encoder_block_backward_workspace_bytes")) return rc;
-  BlockPlan P;
-  if (int rc = block_plan(s, mode_of(dims->dtype), dims->dtype, &P)) return rc;
-  *bytes = P.total;
-  return VTD_OK;
-}
-
-int vtd_encoder_block_backward(const vtd_block_dims* dims, const vtd_block_params* params,
-                               const float* x_dev, const float* dy_dev, float* y_dev,
-                               const vtd_block_grads* grads, void* ws, size_t ws_bytes,
-                               void* stream) {
-  return encoder_block_backward(dims, params, x_dev, dy_dev, y_dev, grads, ws, ws_bytes, stream);
-}
-
-int vtd_encoder_block_backward_dropout(const vtd_block_dims* dims, const vtd_block_params* params,
-                                       const float* x_dev, const float* dy_dev, float* y_dev,
-                                       const vtd_block_grads* grads, void* ws, size_t ws_bytes,
-                                       void* stream, const vtd_block_dropout* drop) {
-  VTD_CHECK_ARG(drop, "encoder_block_backward_dropout: null dropout description");
-  VTD_CHECK_ARG(drop->rate >= 0.f && drop->rate < 1.f,
-                "encoder_block_backward_dropout: dropout rate must be in [0, 1)");
-  return encoder_block_backward(dims, params, x_dev, dy_dev, y_dev, grads, ws, ws_bytes, stream,
-                                drop);
-}
-
-}  // extern "C"
-
 extern "C" {
 
 int vtd_forward(const vtd_config* cfg, const vtd_weights* w, const float* images,
@@ -1495,35 +834,6 @@ int vtd_forward_encoded(const vtd_config* cfg, const vtd_weights* w, const float
   return run_forward(cfg, w, images, nullptr, nullptr, encoded, workspace, workspace_bytes,
                      stream_);
 }
-
-int vtd_head_backward_workspace_bytes(const vtd_config* cfg, size_t* bytes) {
-  VTD_CHECK_ARG(bytes, "null bytes pointer");
-  vtd_dims d;
-  if (int rc = head_mode(cfg, &d, "head_backward_workspace_bytes")) return rc;
-  *bytes = head_plan(d, mode_of(cfg->dtype)).total;
-  return VTD_OK;
-}
-
-int vtd_head_backward(const vtd_config* cfg, const vtd_head_params* w, const float* encoded_dev,
-                      const float* dlogits_dev, float* logits_dev, const vtd_head_grads* g,
-                      void* ws, size_t ws_bytes, void* stream) {
-  return head_backward(cfg, w, encoded_dev, dlogits_dev, logits_dev, g, ws, ws_bytes, stream);
-}
-
-int vtd_head_backward_dropout(const vtd_config* cfg, const vtd_head_params* w,
-                              const float* encoded_dev, const float* dlogits_dev,
-                              float* logits_dev, const vtd_head_grads* g, void* ws,
-                              size_t ws_bytes, void* stream, const vtd_block_dropout* drop) {
-  VTD_CHECK_ARG(drop, "head_backward_dropout: null dropout description");
-  VTD_CHECK_ARG(drop->rate >= 0.f && drop->rate < 1.f,
-                "head_backward_dropout: dropout rate must be in [0, 1)");   // NaN fails
-  return head_backward(cfg, w, encoded_dev, dlogits_dev, logits_dev, g, ws, ws_bytes, stream,
-                       drop);
-}
-
-}  // extern "C"
-
-extern "C" {
 
 int vtd_profile_enable(int enable) {
   ProfState& p = prof();

@@ -97,10 +97,6 @@ __global__ __launch_bounds__(256) void stem_pos_reduce_kernel(const float* __res
 struct StemShape {
   int64_t rows;
   int B, H, W, C, p, D, Dp, T, P, Pp;
-  bool x3;
-  size_t eop;                                        // bytes per logical operand element
-  int ka(int k) const { return x3 ? 2 * k : k; }     // stored width of a k-wide A / G row
-  int kk(int k) const { return x3 ? 3 * k : k; }     // the GEMM's K for it
 };
 int stem_shape(const vtd_stem_dims* c, StemShape* s, const char* what) {
   const std::string w(what);
@@ -121,8 +117,6 @@ int stem_shape(const vtd_stem_dims* c, StemShape* s, const char* what) {
   s->T = (int)T; s->P = (int)P;
   s->Dp = (int)round_up(s->D, VTD_KALIGN);
   s->Pp = (int)round_up(P, VTD_KALIGN);
-  s->x3 = c->dtype == VTD_BF16X3;
-  s->eop = s->x3 ? 4 : 2;
   return VTD_OK;
 }
 
@@ -132,23 +126,18 @@ struct StemPlan {
   size_t patches, wt, gop, rowsum, part, part_bytes, total;
   int msplit;
 };
-StemPlan stem_plan(const StemShape& s, int dtype) {
+StemPlan stem_plan(const StemShape& s, const Mode& m) {
   StemPlan p{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) / 256 * 256;
-    return o;
-  };
+  Arena ar;
   const size_t R = (size_t)s.rows;
-  p.patches = take(R * s.Pp * s.eop);
-  p.wt = take((size_t)s.Dp * s.kk(s.Pp) * 2);
-  p.gop = take(R * s.Dp * s.eop);
-  p.rowsum = take(R * 4);
-  p.msplit = gemm_wgrad_choice((int)s.rows, s.P, s.D, dtype);
+  p.patches = ar.take(R * s.Pp * m.eop);
+  p.wt = ar.take((size_t)s.Dp * m.kk(s.Pp) * 2);
+  p.gop = ar.take(R * s.Dp * m.eop);
+  p.rowsum = ar.take(R * 4);
+  p.msplit = gemm_wgrad_choice((int)s.rows, s.P, s.D, m.op);
   p.part_bytes = p.msplit > 1 ? (size_t)p.msplit * (s.P + 1) * s.D * 4 : 0;
-  p.part = take(p.part_bytes);
-  p.total = off;
+  p.part = ar.take(p.part_bytes);
+  p.total = ar.off;
   return p;
 }
 
@@ -184,28 +173,31 @@ int stem_backward(const vtd_stem_dims* c, const vtd_stem_params* w, const float*
                     (!dx0 || (al(g->pos, 4) && al(g->w, 4) && al(g->b, 4))),
                 "stem_backward: misaligned pointer (workspace, x0, params->w, params->b: 16 "
                 "bytes; every other array: 4)");
-  const StemPlan P = stem_plan(s, c->dtype);
+  const Mode m = mode_of(c->dtype);
+  const StemPlan P = stem_plan(s, m);
   if (ws_bytes < P.total)
     return fail(VTD_ERR_WORKSPACE, "stem_backward: workspace too small (need " +
                                        std::to_string(P.total) + " bytes)");
   hipStream_t st = static_cast<hipStream_t>(stream_);
   char* ws = static_cast<char*>(ws_);
-  const int op = c->dtype, R = (int)s.rows;
+  // the chain context (no padded bias, no input-gradient GEMM: no bias / wkn buffers)
+  const Chain ch{st, ws, m, m.op, reinterpret_cast<float*>(ws + P.part), P.part_bytes, nullptr,
+                 ws + P.wt, nullptr};
+  const int R = (int)s.rows;
   void* patches = ws + P.patches;
   int rc;
   // ================= training forward
-  if ((rc = patches_launch(images, s.B, s.H, s.W, s.C, s.p, patches, s.ka(s.Pp), op, st)))
+  if ((rc = patches_launch(images, s.B, s.H, s.W, s.C, s.p, patches, m.ka(s.Pp), m.op, st)))
     return rc;
   if (x0) {                            // (with dx0: only when the caller asks for x0)
-    void* wt = ws + P.wt;
-    if ((rc = transpose_op_launch(w->w, s.P, s.D, wt, s.Pp, s.Dp, op, st))) return rc;
+    if ((rc = ch.conv_t(w->w, s.P, s.D, s.Pp, s.Dp))) return rc;
     vtd_epilogue e{};
     e.bias = w->b;
     e.rowadd = w->pos; e.rowadd_period = s.T; e.rowadd_ncols = s.D;
     e.act = VTD_ACT_NONE;
     e.out = x0; e.ldo = s.D; e.out_dtype = VTD_F32;
-    if ((rc = gemm_launch(R, s.D, s.kk(s.Pp), patches, s.ka(s.Pp), wt, s.kk(s.Pp), op, &e, st,
-                          2.0 * R * (double)s.P * s.D)))
+    if ((rc = ch.gemm(R, s.D, m.kk(s.Pp), patches, m.ka(s.Pp), ch.wt, 1, e,
+                      2.0 * R * (double)s.P * s.D)))
       return rc;
   }
   if (!dx0) return VTD_OK;
@@ -213,11 +205,9 @@ int stem_backward(const vtd_stem_dims* c, const vtd_stem_params* w, const float*
   // ================= backward
   void* gop = ws + P.gop;
   float* rowsum = reinterpret_cast<float*>(ws + P.rowsum);
-  if ((rc = stem_grad_rows_launch(dx0, s.rows, s.D, gop, s.ka(s.Dp), s.Dp, s.x3, rowsum, st)))
+  if ((rc = stem_grad_rows_launch(dx0, s.rows, s.D, gop, m.ka(s.Dp), s.Dp, m.x3, rowsum, st)))
     return rc;
-  if ((rc = gemm_wgrad_launch(R, s.P, s.D, patches, s.ka(s.Pp), gop, s.ka(s.Dp), op, g->w, s.D,
-                              g->b, reinterpret_cast<float*>(ws + P.part), P.part_bytes,
-                              P.msplit, st)))
+  if ((rc = ch.wgrad(R, s.P, s.D, patches, m.ka(s.Pp), gop, m.ka(s.Dp), g->w, s.D, g->b, P.msplit)))
     return rc;
   ProfScope ps(st, PROF_OTHER, 0.0);
   hipLaunchKernelGGL(stem_pos_reduce_kernel, dim3((unsigned)((s.T + 255) / 256)), dim3(256), 0, st,
@@ -236,7 +226,7 @@ int vtd_stem_backward_workspace_bytes(const vtd_stem_dims* dims, size_t* bytes) 
   VTD_CHECK_ARG(bytes, "null bytes pointer");
   vtd::StemShape s;
   if (int rc = vtd::stem_shape(dims, &s, "stem_backward_workspace_bytes")) return rc;
-  *bytes = vtd::stem_plan(s, dims->dtype).total;
+  *bytes = vtd::stem_plan(s, vtd::mode_of(dims->dtype)).total;
   return VTD_OK;
 }
 
