@@ -890,6 +890,30 @@ int vtd_stem_backward_workspace_bytes(const vtd_stem_dims* dims, size_t* bytes);
 int vtd_stem_backward(const vtd_stem_dims* dims, const vtd_stem_params* params,
                       const float* images_dev, const float* dx0_dev, float* x0_dev,
                       const vtd_stem_grads* grads, void* ws, size_t ws_bytes, void* stream);
+/* The image gradient (an addition to ABI 17; DESIGN.md "Image gradient"): dimages_dev fp32
+ * [batch][H][W][C] = d loss / d images from dx0_dev fp32 [batch tokens][d] = d loss / d x0 and
+ * w_dev, the linear_projection kernel in the Keras layout [patch_dim][d].  dims as above; the
+ * images themselves are not read (the stem is linear in them).  Launches: the pass over dx0 of
+ * vtd_stem_backward (its rows in operand form; the row sums go to scratch), the kernel converted
+ * to the mode's B operand as stored ([patch_dim_p][d_p], what vtd_head_backward makes for its
+ * input gradients), one vtd_gemm dP = dx0 W^T into fp32 [batch tokens][patch_dim_p] in the
+ * workspace, and one kernel that applies the adjoint of tf.image.extract_patches(SAME):
+ *   dimages[b][y][x][c] = dP[b tokens + py gw + px][(ky patch + kx) C + c],
+ *   py = (y + pad_top) / patch, ky = (y + pad_top) % patch, likewise in x, pad_before =
+ *   floor(pad / 2) as vtd_extract_patches pads.
+ * Every image element has one source and is written once; the gradient that falls on the zero
+ * pad is dropped.  Asynchronous on `stream` (one stream), no allocation, no host
+ * synchronisation, no atomics, bit-identical from run to run; exactly the elements of
+ * dimages_dev are written.  vtd_stem_backward and this entry share nothing: each has its own
+ * workspace size, and neither changes the other's outputs.
+ * VTD_ERR_INVALID_ARG before any device call: a null dims / w / dx0 / dimages / workspace
+ * pointer, non-positive sizes, batch * tokens >= 2^31, d or patch_dim of 2^24 or more, a
+ * workspace or w_dev not 16-byte aligned, dx0_dev or dimages_dev not 4-byte aligned;
+ * VTD_ERR_UNSUPPORTED: a dtype other than the two; ws_bytes <
+ * vtd_stem_image_grad_workspace_bytes (a multiple of 256, monotone in batch): VTD_ERR_WORKSPACE. */
+int vtd_stem_image_grad_workspace_bytes(const vtd_stem_dims* dims, size_t* bytes);
+int vtd_stem_image_grad(const vtd_stem_dims* dims, const float* w_dev, const float* dx0_dev,
+                        float* dimages_dev, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- optimizer step: keras.optimizers.Adam + the ClipWeight constraint + the operand re-pack,
  * ONE kernel over a table of tensors.  The table entry is vtd_train_tensor (below);

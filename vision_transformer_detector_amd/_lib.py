@@ -302,6 +302,10 @@ SIGNATURES = {
     "vtd_stem_backward": (c_int, [ctypes.POINTER(VtdStemDims), ctypes.POINTER(VtdStemParams),
                                   c_void_p, c_void_p, c_void_p, ctypes.POINTER(VtdStemParams),
                                   c_void_p, c_size_t, c_void_p]),
+    "vtd_stem_image_grad_workspace_bytes": (c_int, [ctypes.POINTER(VtdStemDims),
+                                                    ctypes.POINTER(c_size_t)]),
+    "vtd_stem_image_grad": (c_int, [ctypes.POINTER(VtdStemDims), c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
     "vtd_adam_plan_bytes":(c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int,
                                     ctypes.POINTER(c_size_t), ctypes.POINTER(c_int)]),
     "vtd_adam_plan_upload": (c_int, [ctypes.POINTER(VtdAdamTensor), c_int, c_int, c_void_p,

@@ -6,6 +6,9 @@
 // vtd_gemm_wgrad) and dpos[n] = sum_b sum_j dx0[b N + n][j]; the two kernels here make the G
 // operand of that product and the row sums in ONE pass over dx0, and reduce the row sums over
 // the batch.  No atomics, one writer per element, every sum in a fixed order.
+// vtd_stem_image_grad: d loss / d images = the adjoint of the extraction applied to dP = dx0 W^T
+// (the same pass over dx0, the kernel in its Keras [K][N] form as Bt, one vtd_gemm, then
+// stem_unpatch_kernel).
 #include <algorithm>
 
 #include "vtd_launch.h"
@@ -216,6 +219,118 @@ int stem_backward(const vtd_stem_dims* c, const vtd_stem_params* w, const float*
   return VTD_OK;
 }
 
+// ------------------------------------------------------------------ image gradient
+// The adjoint of the SAME-padded patch extraction (patches_kernel, vtd_elementwise.hip): every
+// image element was copied to exactly one patch column, so its gradient is that column of
+//   dP fp32 [B T][ldp]:  dimg[b][y][x][c] = dP[b T + py gw + px][(ky p + kx) C + c],
+//   py = (y + top) / p, ky = (y + top) % p, px = (x + left) / p, kx = (x + left) % p.
+// One wave per image row (b, y): py and ky are the wave's, and along the row position
+// i = x C + c the source is dP[b T + py gw + j / pC][ky pC + j % pC] with j = i + left C --
+// runs of pC consecutive floats on both sides.  Lane l takes the positions l V, (l + 64) V, ...:
+// consecutive lanes write consecutive addresses.  The pad columns of dP are never read, every
+// element of dimg is written once, nothing else is.
+// VEC (V = 4): W C, p C and left C are multiples of 4 and dimg is 16-B aligned (dP is, with
+// ldp % 4 == 0), so every group of 4 positions lies inside one run and both sides are one
+// aligned 16-B access.  The generic path (V = 1) moves the same values float by float.
+template <bool VEC>
+__global__ __launch_bounds__(256) void stem_unpatch_kernel(const float* __restrict__ dP, int ldp,
+                                                           int64_t rows, int H, int64_t WC,
+                                                           int pC, int p, int gw, int T, int top,
+                                                           int64_t leftC,
+                                                           float* __restrict__ dimg) {
+  constexpr int V = VEC ? 4 : 1;
+  const int lane = threadIdx.x & 63;
+  for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows;
+       r += (int64_t)gridDim.x * 4) {
+    const int64_t b = r / H;
+    const int yy = (int)(r - b * H) + top;
+    const int py = yy / p, ky = yy - py * p;
+    const float* src = dP + (b * T + (int64_t)py * gw) * ldp + (int64_t)ky * pC;
+    float* dst = dimg + r * WC;
+    for (int64_t i = (int64_t)lane * V; i < WC; i += 64 * V) {
+      const int64_t j = i + leftC, run = j / pC;
+      const float* s = src + run * ldp + (j - run * pC);
+      if constexpr (VEC)
+        *reinterpret_cast<f32x4*>(dst + i) = *reinterpret_cast<const f32x4*>(s);
+      else
+        dst[i] = *s;
+    }
+  }
+}
+
+// Workspace of vtd_stem_image_grad: buffers in use order, 256-B aligned, each linear in the rows.
+struct ImageGradPlan {
+  size_t gop, rowsum, wkn, dp, total;
+};
+ImageGradPlan image_grad_plan(const StemShape& s, const Mode& m) {
+  ImageGradPlan p{};
+  Arena ar;
+  const size_t R = (size_t)s.rows;
+  p.gop = ar.take(R * s.Dp * m.eop);
+  p.rowsum = ar.take(R * 4);                       // stem_grad_rows' second output: scratch here
+  p.wkn = ar.take((size_t)s.Pp * m.kk(s.Dp) * 2);
+  p.dp = ar.take(R * s.Pp * 4);
+  p.total = ar.off;
+  return p;
+}
+
+int stem_unpatch_launch(const float* dP, const StemShape& s, float* dimg, hipStream_t st) {
+  const int64_t gh = ((int64_t)s.H + s.p - 1) / s.p, gw = ((int64_t)s.W + s.p - 1) / s.p;
+  // pad_before = floor(pad / 2), as patches_launch splits it (pad < p)
+  const int top = (int)(gh * s.p - s.H) / 2, left = (int)(gw * s.p - s.W) / 2;
+  const int pC = s.p * s.C;
+  const int64_t rows = (int64_t)s.B * s.H, WC = (int64_t)s.W * s.C, leftC = (int64_t)left * s.C;
+  const bool vec = WC % 4 == 0 && pC % 4 == 0 && leftC % 4 == 0 && s.Pp % 4 == 0 &&
+                   reinterpret_cast<uintptr_t>(dimg) % 16 == 0 &&
+                   reinterpret_cast<uintptr_t>(dP) % 16 == 0;
+  const int grid = (int)std::min<int64_t>((rows + 3) / 4, 65536);
+  ProfScope ps(st, PROF_OTHER, 0.0);
+  if (vec)
+    hipLaunchKernelGGL(stem_unpatch_kernel<true>, dim3(grid), dim3(256), 0, st, dP, s.Pp, rows,
+                       s.H, WC, pC, s.p, (int)gw, s.T, top, leftC, dimg);
+  else
+    hipLaunchKernelGGL(stem_unpatch_kernel<false>, dim3(grid), dim3(256), 0, st, dP, s.Pp, rows,
+                       s.H, WC, pC, s.p, (int)gw, s.T, top, leftC, dimg);
+  VTD_LAUNCH_CHECK("stem_unpatch");
+  return VTD_OK;
+}
+
+int stem_image_grad(const vtd_stem_dims* c, const float* w, const float* dx0, float* dimg,
+                    void* ws_, size_t ws_bytes, void* stream_) {
+  StemShape s;
+  if (int rc = stem_shape(c, &s, "stem_image_grad")) return rc;
+  VTD_CHECK_ARG(w && dx0 && dimg && ws_, "stem_image_grad: null pointer");
+  // the workspace holds operand rows and dP, the kernel is converted in 16-B vectors; dx0 and
+  // the images are read and written float by float where they are not 16-B aligned
+  auto al = [](const void* q, uintptr_t a) { return reinterpret_cast<uintptr_t>(q) % a == 0; };
+  VTD_CHECK_ARG(al(ws_, 16) && al(w, 16) && al(dx0, 4) && al(dimg, 4),
+                "stem_image_grad: misaligned pointer (workspace, w: 16 bytes; dx0, dimages: 4)");
+  const Mode m = mode_of(c->dtype);
+  const ImageGradPlan P = image_grad_plan(s, m);
+  if (ws_bytes < P.total)
+    return fail(VTD_ERR_WORKSPACE, "stem_image_grad: workspace too small (need " +
+                                       std::to_string(P.total) + " bytes)");
+  hipStream_t st = static_cast<hipStream_t>(stream_);
+  char* ws = static_cast<char*>(ws_);
+  // the chain context (one unsplit input-gradient GEMM: no partials, bias or W^T buffers)
+  const Chain ch{st, ws, m, m.op, nullptr, 0, nullptr, nullptr, ws + P.wkn};
+  const int R = (int)s.rows;
+  void* gop = ws + P.gop;
+  float* dP = reinterpret_cast<float*>(ws + P.dp);
+  int rc;
+  if ((rc = stem_grad_rows_launch(dx0, s.rows, s.D, gop, m.ka(s.Dp), s.Dp, m.x3,
+                                  reinterpret_cast<float*>(ws + P.rowsum), st)))
+    return rc;
+  if ((rc = ch.conv_kn(w, s.P, s.D, s.Pp, s.Dp))) return rc;
+  vtd_epilogue e{};
+  e.act = VTD_ACT_NONE;
+  e.out = dP; e.ldo = s.Pp; e.out_dtype = VTD_F32;
+  if ((rc = ch.gemm(R, s.P, m.kk(s.Dp), gop, m.ka(s.Dp), ch.wkn, 1, e,
+                    2.0 * R * (double)s.P * s.D)))
+    return rc;
+  return stem_unpatch_launch(dP, s, dimg, st);
+}
+
 }  // namespace
 
 }  // namespace vtd
@@ -235,6 +350,19 @@ int vtd_stem_backward(const vtd_stem_dims* dims, const vtd_stem_params* params,
                       const vtd_stem_grads* grads, void* ws, size_t ws_bytes, void* stream) {
   return vtd::stem_backward(dims, params, images_dev, dx0_dev, x0_dev, grads, ws, ws_bytes,
                             stream);
+}
+
+int vtd_stem_image_grad_workspace_bytes(const vtd_stem_dims* dims, size_t* bytes) {
+  VTD_CHECK_ARG(bytes, "null bytes pointer");
+  vtd::StemShape s;
+  if (int rc = vtd::stem_shape(dims, &s, "stem_image_grad_workspace_bytes")) return rc;
+  *bytes = vtd::image_grad_plan(s, vtd::mode_of(dims->dtype)).total;
+  return VTD_OK;
+}
+
+int vtd_stem_image_grad(const vtd_stem_dims* dims, const float* w_dev, const float* dx0_dev,
+                        float* dimages_dev, void* ws, size_t ws_bytes, void* stream) {
+  return vtd::stem_image_grad(dims, w_dev, dx0_dev, dimages_dev, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -802,7 +802,7 @@ class Model:
         names = list(self.weight_shapes)[:3 + self.kwargs["encoder_repeat_times"] * per]
         return self._device_master("encoder", names)
 
-    def gradients(self, images, y_true, step=0):
+    def gradients(self, images, y_true, step=0, image_gradient=False):
         """The gradient of the compiled loss with respect to every weight: the training forward
         of the whole model, the loss gradient at its logits, and the backward through the head,
         every encoder block in reverse and the patch embedding.  Returns (out5, grads): out5 as
@@ -819,16 +819,30 @@ class Model:
         and compiled with a `dropout_seed` every dropout site of the reference's training graph
         is on (vtd_encoder_block_backward_dropout with site_base = i (1 + q) for block i,
         vtd_head_backward_dropout with site_base = L (1 + q)), the masks those of (seed, `step`,
-        site): the same step gives the same bits; otherwise `step` is not used.  Needs
-        compile(loss=my_custom_loss or a functools.partial of it) and dtype 'bf16x3' or
-        'bfloat16'."""
-        return self._grad_chain("gradients", images, y_true, step=step)
+        site): the same step gives the same bits; otherwise `step` is not used.
+        image_gradient=True: `grads` gains one last key, "images" -- d loss / d images, an fp32
+        (B, H, W, C) device tensor, of the float32 images the chain read (after `_as_images`) --
+        from one vtd_stem_image_grad call on the first block's input gradient, after the stem's
+        backward; out5 and every other entry keep their bits.  Needs compile(loss=my_custom_loss
+        or a functools.partial of it) and dtype 'bf16x3' or 'bfloat16'."""
+        return self._grad_chain("gradients", images, y_true, step=step,
+                                image_gradient=image_gradient)
 
-    def _grad_chain(self, what, images, y_true, buffers=None, step=0):
+    def image_gradient(self, images, y_true, step=0):
+        """(out5, dimages): the loss terms and d loss / d images, fp32 (B, H, W, C) -- what a
+        saliency map, a sign-gradient step on the inputs or an input optimisation starts from.
+        The chain of gradients(..., image_gradient=True), weight gradients included (there is no
+        backward that skips them), and the bits of its "images" entry; dropout and `step` as
+        there."""
+        out5, grads = self._grad_chain("image_gradient", images, y_true, step=step,
+                                       image_gradient=True)
+        return out5, grads["images"]
+
+    def _grad_chain(self, what, images, y_true, buffers=None, step=0, image_gradient=False):
         """The chain gradients and train_on_batch share.  `buffers`: Keras name -> fp32 device
         tensor to write each weight gradient into (the optimizer's persistent ones); None
         allocates fresh tensors.  `step`: the dropout step (`_call_dropout`).  Returns (out5,
-        grads keyed by `weight_names()`)."""
+        grads keyed by `weight_names()`, then "images" with `image_gradient`)."""
         self._require(what)
         drop = self._call_dropout(what, step)
         from . import encoder as _enc
@@ -878,7 +892,15 @@ class Model:
             _, g = _stem.run(x, sw, sdims, dx0=dy, want_x0=False, ws=stem_ws,
                              out=None if into is None else (None, into[:3]))
             found = g + found + list(head.values())
-        return out5, OrderedDict(zip(self.weight_shapes, found))
+            grads = OrderedDict(zip(self.weight_shapes, found))
+            if image_gradient:
+                n = _stem.image_grad_workspace_bytes(sdims)
+                ws = getattr(self, "_image_grad_ws", None)
+                if ws is None or ws.numel() < n:
+                    ws = self._image_grad_ws = torch.empty(n, dtype=torch.uint8,
+                                                           device=self.device)
+                grads["images"] = _stem.image_grad(dy, sw[1], sdims, ws=ws)
+        return out5, grads
 
     # ---- what the gradient and training calls share
     def _require(self, what, mode=True, loss=True, optimizer=False, whole_model=False):

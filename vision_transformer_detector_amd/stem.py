@@ -4,8 +4,9 @@ patch_embedding(images, weights, ...) is the reference's transformer_preprocesso
 (vtd.py:271-307): tf.image.extract_patches (SAME), the linear projection and the position
 embedding add, from the three Keras weights in their Keras shapes.  Forward and backward are one
 vtd_stem_backward call each (include/vtd.h): the forward keeps only the images and the weights,
-the backward extracts the patches again and fills the three weight gradients.  There is no
-fallback: what the kernels do not cover raises.
+the backward extracts the patches again and fills the three weight gradients.  The gradient of
+the images is opt-in (`image_gradient=True`): one more call, vtd_stem_image_grad (`image_grad`).
+There is no fallback: what the kernels do not cover raises.
 """
 from __future__ import annotations
 
@@ -83,16 +84,41 @@ def run(images, weights, dims: L.VtdStemDims, dx0=None, want_x0=True, ws=None, o
     return x0, grads
 
 
+def image_grad_workspace_bytes(dims: L.VtdStemDims) -> int:
+    n = L.c_size_t(0)
+    L.check(L.lib.vtd_stem_image_grad_workspace_bytes(ctypes.byref(dims), ctypes.byref(n)),
+            "vtd_stem_image_grad_workspace_bytes")
+    return int(n.value)
+
+
+def image_grad(dx0, w, dims: L.VtdStemDims, ws=None, out=None):
+    """vtd_stem_image_grad on contiguous fp32 device tensors: dx0 (B, N, d) = d loss / d x0 and
+    w, the linear_projection kernel (patch_dim, d).  Returns d loss / d images, fp32 (B, H, W, C).
+    ws: a uint8 workspace of at least image_grad_workspace_bytes(dims).  out: the caller's own
+    output tensor in place of a new one."""
+    if ws is None:
+        ws = torch.empty(image_grad_workspace_bytes(dims), device=dx0.device, dtype=torch.uint8)
+    dimages = out if out is not None else torch.empty(
+        (dims.batch, dims.H, dims.W, dims.C), device=dx0.device, dtype=torch.float32)
+    with torch.cuda.device(dx0.device):
+        L.check(L.lib.vtd_stem_image_grad(
+            ctypes.byref(dims), w.data_ptr(), dx0.data_ptr(), dimages.data_ptr(), ws.data_ptr(),
+            ws.numel(), L.stream_ptr()), "vtd_stem_image_grad")
+    return dimages
+
+
 class _PatchEmbedding(torch.autograd.Function):
     """Forward: the C entry with dx0 = NULL, keeping the images and the weights only.  Backward:
-    one C call that extracts the patches again and fills the weight gradients."""
+    one C call that extracts the patches again and fills the weight gradients; with
+    `image_gradient` and images that require grad, one vtd_stem_image_grad call as well."""
 
     @staticmethod
-    def forward(ctx, images, dims, *weights):
+    def forward(ctx, images, dims, image_gradient, *weights):
         xd = images.detach()
         wd = [t.detach().contiguous() for t in weights]
         x0, _ = run(xd, wd, dims)
         ctx.dims = dims
+        ctx.image_gradient = image_gradient
         ctx.save_for_backward(xd, *wd)
         return x0
 
@@ -103,11 +129,13 @@ class _PatchEmbedding(torch.autograd.Function):
         dx0 = gx0.to(torch.float32).reshape(xd.shape[0], -1, ctx.dims.d).contiguous()
         need = ctx.needs_input_grad
         _, grads = run(xd, wd, ctx.dims, dx0=dx0, want_x0=False)
-        return (None, None) + tuple(g if n else None for g, n in zip(grads, need[2:]))
+        dimages = image_grad(dx0, wd[1], ctx.dims) if ctx.image_gradient and need[0] else None
+        return (dimages, None, None) + tuple(g if n else None for g, n in zip(grads, need[3:]))
 
 
-def patch_embedding(images, weights, *, patch_size, dtype="bf16x3"):
-    """The patch embedding (vtd.py:271-307), differentiable w.r.t. its three weights.
+def patch_embedding(images, weights, *, patch_size, dtype="bf16x3", image_gradient=False):
+    """The patch embedding (vtd.py:271-307), differentiable w.r.t. its three weights and, on
+    request, its images.
 
     images: float32 device tensor (B, H, W, C).  weights: a sequence (or an OrderedDict, whose
     values are taken) of float32 device tensors in Keras creation order and shapes: the position
@@ -116,8 +144,12 @@ def patch_embedding(images, weights, *, patch_size, dtype="bf16x3"):
     so).  dtype: 'bf16x3' or 'bfloat16', the operand mode of the two products; x0 and every
     gradient are float32.  Returns x0 (B, tokens, d), the input of the first `encoder_block`;
     backward() makes one vtd_stem_backward call, bit-identical from run to run, with no
-    synchronisation; weights that do not require grad get None, and so do the images (the image
-    gradient is not computed)."""
+    synchronisation; weights that do not require grad get None.  image_gradient: False (the
+    default) leaves `images.grad` None whatever the images require; True, with images that
+    require grad, makes backward() also fill `images.grad` = d loss / d images, fp32 (B, H, W, C),
+    with one vtd_stem_image_grad call (dx0 W^T in the mode's operands, then the adjoint of the
+    patch extraction: the gradient that falls on the SAME zero pad is dropped), bit-identical from
+    run to run.  The weight gradients and x0 have the same bits either way."""
     if isinstance(weights, dict):
         weights = list(weights.values())
     else:
@@ -153,4 +185,4 @@ def patch_embedding(images, weights, *, patch_size, dtype="bf16x3"):
             raise ValueError(f"patch_embedding: {what} has shape {tuple(t.shape)}, expected "
                              f"{shape}")
     dims = L.VtdStemDims(batch=B, H=H, W=W, C=C, patch=int(patch_size), d=d, dtype=code)
-    return _PatchEmbedding.apply(images.contiguous(), dims, *weights)
+    return _PatchEmbedding.apply(images.contiguous(), dims, bool(image_gradient), *weights)
