@@ -1030,6 +1030,65 @@ int vtd_fold_plan_upload(const vtd_fold_job* jobs, int n_jobs, int dtype, void* 
 int vtd_fold_layernorm_batch(const void* plan_dev, int n_jobs, int max_rows, int dtype,
                              void* stream);
 
+/* Numerical health (csrc/vtd_health.hip; DESIGN.md "Numerical health"): one record per tensor of
+ * a table of fp32 device tensors, in ONE pass over their elements -- what the reference's
+ * check_inf_nan / check_weights / CheckModelWeight (vtd.py:46-116, 731-758, 650-687) ask of a
+ * tensor, plus the sum of squares a gradient norm needs.
+ *
+ * A record (vtd_tensor_stat, 48 B) of a tensor x of n elements:
+ *   n                       the element count, as given
+ *   nan, pos_inf, neg_inf   how many elements are NaN / +inf / -inf
+ *   max, min                over the elements that are not NaN, infinities included, by
+ *                           comparison (x > max, x < min; never fmax / fmin); with no such element
+ *                           max = -inf and min = +inf.  +0 and -0 compare equal: the sign of a
+ *                           zero result is unspecified.  Subnormals are kept, not flushed.
+ *   sumsq                   the sum of (double)x * (double)x over the FINITE elements: each value
+ *                           converted to fp64 before the multiply, so every square is exact and
+ *                           fused or unfused multiply-add give the same bits; every partial sum
+ *                           is fp64.  All terms are >= 0 and exact, so whatever the order the
+ *                           result is within n * 2^-53 relative of the exact sum.
+ * out: NULL, or n floats that receive out[i] = x[i] != x[i] ? replace_nan : x[i] in the same pass
+ * (every non-NaN element, infinities included, keeps its bits); out may alias x.  With out NULL
+ * nothing but the records and the workspace is written.
+ *
+ * Structure: no atomics, the same bits on every run.  A workgroup (256 threads) takes one chunk
+ * of VTD_STATS_CHUNK elements of one tensor, counted from that tensor's element 0, through the
+ * plan's chunk -> (tensor, chunk index) map; each thread sums its elements in index order, the
+ * workgroup reduces in a fixed tree and writes one 32-B partial record to `workspace`; a second
+ * kernel on the same stream folds each tensor's partials -- lane l of one wave takes chunks l,
+ * l + 64, ... in that order, then the same fixed tree -- into stats_dev[t].  Chunking restarts per
+ * tensor, so a tensor's record depends on its elements, n and the alignment of its bases (which
+ * picks the vector width: 16-B loads when x, out and 4 n are multiples of 16, else 8 B likewise,
+ * else 4 B) and not on what else is in the table or where it sits.
+ *
+ * vtd_stats_plan_bytes: the bytes of the device plan, the bytes of the workspace (32 per chunk)
+ * and the chunk count, sum over the tensors of ceil(n / VTD_STATS_CHUNK).  vtd_stats_plan_upload
+ * builds the plan and copies it to plan_dev (caller-owned, 16-B aligned) on `stream`, waiting for
+ * the copy -- the only synchronising entry.  vtd_tensor_stats: two launches on `stream`, no copy,
+ * no allocation, no host synchronisation; stats_dev: n_tensors records in device memory.
+ * VTD_ERR_INVALID_ARG before any device call: a null table or null outputs, n_tensors <= 0, a
+ * null x, n <= 0, x or out not 4-B aligned, more chunks than an int holds; plan_bytes too small, a
+ * null or not 16-B aligned plan_dev; chunks <= 0, a null or not 8-B aligned workspace / stats_dev,
+ * workspace_bytes too small. */
+#define VTD_STATS_CHUNK 16384
+typedef struct vtd_stats_tensor {
+  const float* x;
+  float* out;                /* NULL, or n floats; may alias x */
+  int64_t n;
+} vtd_stats_tensor;
+typedef struct vtd_tensor_stat {
+  float max, min;
+  int64_t n, nan, pos_inf, neg_inf;
+  double sumsq;
+} vtd_tensor_stat;
+int vtd_stats_plan_bytes(const vtd_stats_tensor* tensors, int n_tensors, size_t* plan_bytes,
+                         size_t* workspace_bytes, int* chunks);
+int vtd_stats_plan_upload(const vtd_stats_tensor* tensors, int n_tensors, void* plan_dev,
+                          size_t plan_bytes, void* stream);
+int vtd_tensor_stats(const void* plan_dev, int n_tensors, int chunks, void* workspace,
+                     size_t workspace_bytes, vtd_tensor_stat* stats_dev, float replace_nan,
+                     void* stream);
+
 /* Optional per-kernel timing of vtd_forward (hipEvents on `stream`, recorded around
  * every launch while enabled).  vtd_profile_read returns per-class totals in ms
  * summed over the forwards since the last reset; classes: 0 gemm, 1 attention,

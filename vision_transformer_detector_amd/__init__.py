@@ -47,6 +47,9 @@ from .stem import patch_embedding  # noqa: F401
 from . import optimizers, presets  # noqa: F401
 from .optimizers import _allowed_decay_times, learning_rate_step_decay  # noqa: F401
 from .preprocess import get_image_tensors  # noqa: F401
+from . import health  # noqa: F401
+from .health import (CheckModelWeight, TensorStat, check_inf_nan, check_weights,  # noqa: F401
+                     tensor_stats)
 
 __all__ = ["Constants", "Model", "create_vision_transformer_detector",
            "transform_predictions", "decode_detections", "detection_list", "presets",
@@ -55,4 +58,5 @@ __all__ = ["Constants", "Model", "create_vision_transformer_detector",
            "diagonal_calculator", "get_label_arrays", "optimizers",
            "learning_rate_step_decay", "attention_core", "dropout", "dropout_mask", "layer_norm",
            "encoder_block",
-           "patch_embedding", "enable_device_kernel_arguments"]
+           "patch_embedding", "enable_device_kernel_arguments", "health", "tensor_stats",
+           "TensorStat", "check_weights", "check_inf_nan", "CheckModelWeight"]

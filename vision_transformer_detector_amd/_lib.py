@@ -163,6 +163,19 @@ class VtdFoldJob(ctypes.Structure):
                 [(n, c_int) for n in ("N", "K", "ldw", "ldo")])
 
 
+class VtdStatsTensor(ctypes.Structure):
+    """vtd_stats_tensor: `out` None, or n floats for the NaN-replaced copy (may alias x)."""
+    _fields_ = [("x", c_void_p), ("out", c_void_p), ("n", c_int64)]
+
+
+class VtdTensorStat(ctypes.Structure):
+    """vtd_tensor_stat, 48 B (include/vtd.h "Numerical health")."""
+    _fields_ = [("max", c_float), ("min", c_float), ("n", c_int64), ("nan", c_int64),
+                ("pos_inf", c_int64), ("neg_inf", c_int64), ("sumsq", ctypes.c_double)]
+
+
+STATS_CHUNK = 16384
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "vtd_abi_version": (c_int, []),
@@ -321,6 +334,13 @@ SIGNATURES = {
     "vtd_fold_plan_upload": (c_int, [ctypes.POINTER(VtdFoldJob), c_int, c_int, c_void_p, c_size_t,
                                      ctypes.POINTER(c_int), c_void_p]),
     "vtd_fold_layernorm_batch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "vtd_stats_plan_bytes": (c_int, [ctypes.POINTER(VtdStatsTensor), c_int,
+                                     ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t),
+                                     ctypes.POINTER(c_int)]),
+    "vtd_stats_plan_upload": (c_int, [ctypes.POINTER(VtdStatsTensor), c_int, c_void_p, c_size_t,
+                                      c_void_p]),
+    "vtd_tensor_stats": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_float,
+                                 c_void_p]),
     "vtd_forward": (c_int, [ctypes.POINTER(VtdConfig), ctypes.POINTER(VtdWeights), c_void_p,
                             c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vtd_set_knob": (c_int, [c_int, c_int]),

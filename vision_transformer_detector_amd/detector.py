@@ -160,6 +160,7 @@ class Model:
         self.metrics = []
         self.optimizer = None          # compile(): stored as given, resolved by a training call
         self.dropout_seed = None       # compile(dropout_seed=): dropout in the training graph
+        self.stop_training = False     # set by a callback: fit / fit_head end after that epoch
         self._head_dirty = False       # the head's device masters are ahead of self._master
         self._enc_dirty = False        # so are the encoder's and the stem's (train_on_batch)
         self.set_weights(keras_default_init(self.weight_shapes, seed))
@@ -939,11 +940,14 @@ class Model:
         is called once on the callbacks that have it.  Per epoch: `lr_schedule(epoch, lr)` sets
         the optimizer's rate, the batch losses weighted by batch size add up in a float64[2]
         device accumulator, ONE host read takes the mean into the History, and every callback
-        that has `on_epoch_end` gets (epoch, {"loss": ...})."""
+        that has `on_epoch_end` gets (epoch, {"loss": ...}).  `self.stop_training` is set to False
+        at the start, and the loop ends after the callbacks of an epoch in which one of them set
+        it to True (Keras's convention; health.CheckModelWeight(stop_on_nan=True) does)."""
         from . import optimizers as _opt
         from .metrics import _device_f32
         if int(epochs) < 0:
             raise ValueError(f"{what}: epochs must be >= 0, got {epochs}")
+        self.stop_training = False
         for cb in callbacks:
             if callable(getattr(cb, "set_model", None)):
                 cb.set_model(self)
@@ -968,6 +972,8 @@ class Model:
                 for cb in callbacks:
                     if callable(getattr(cb, "on_epoch_end", None)):
                         cb.on_epoch_end(epoch, {"loss": loss})
+                if self.stop_training:              # a callback asked for the end (Keras)
+                    break
         return hist
 
     # ---- whole-model training (vtd_train_step, vtd_fold_layernorm_batch; optimizers.py)
@@ -1034,7 +1040,7 @@ class Model:
         return out5
 
     def fit_head(self, x, y=None, batch_size=32, epochs=1, lr_schedule=None, cache_features=True,
-                 encoded=None):
+                 encoded=None, callbacks=None):
         """keras.Model.fit for the detection head on a frozen encoder (the notebook's "overfit
         a few images" loop): `epochs` passes of train_head_on_batch over the batches, which are
         formed as `evaluate` forms them (arrays split by `batch_size`, the last may be short; or
@@ -1044,7 +1050,7 @@ class Model:
         `cache_features`: the encoder runs once per batch and later epochs reuse its (B, N, d)
         features (the encoder is frozen, so they cannot change).  `encoded`: the features of
         the whole of `x` (len(x), N, d), as head_gradients takes them; `x` is then not read.
-        Returns an object whose .history["loss"] holds one float per epoch: the mean of the
+        `callbacks`: as `fit` takes them.  Returns an object whose .history["loss"] holds one float per epoch: the mean of the
         batch losses weighted by batch size (the Keras loss metric), accumulated on the device
         and read once per epoch."""
         # the mode and the loss are train_head_on_batch's checks, per batch
@@ -1064,7 +1070,8 @@ class Model:
                 features[i] = self.encode(images)
             feats = features[i] if encoded is not None or cache_features else None
             return self.train_head_on_batch(images, labels, encoded=feats)
-        return self._fit_loop("fit_head", optimizer, batches, step, epochs, lr_schedule)
+        return self._fit_loop("fit_head", optimizer, batches, step, epochs, lr_schedule,
+                              list(callbacks or []))
 
     def _head_pass(self, what, images, y_true, encoded, weight_grads=None, drop=None):
         """The part head_gradients and train_head_on_batch share: the checks, the encoder
@@ -1107,6 +1114,25 @@ class Model:
             _head.run(cfg, encoded, weights, dlogits=dlogits, grads=[grads[n] for n in wdev],
                       d_encoded=grads.get("encoded_images"), ws=self._hb_ws, drop=hdrop)
         return out5, grads
+
+    # ---- numerical health (vtd_tensor_stats; health.py)
+    def weight_stats(self):
+        """The statistics of every weight as it is on the device NOW: an OrderedDict over
+        `weight_names()` of health.TensorStat (NaN / +Inf / -Inf counts, the non-NaN max / min, the
+        fp64 sum of squares and `norm`), read from the device masters (`_encoder_master()` +
+        `_head_master()`) -- after optimizer steps the stepped weights, with no read-back of the
+        weights themselves (`_sync_master` is not called).  One vtd_tensor_stats launch pair and
+        one host read of 48 B per tensor; the uploaded plan and its workspace are kept on the
+        model and rebuilt when set_weights replaces the masters.  Works in every `dtype`."""
+        from . import health as _health
+        held = getattr(self, "_health_plan", None)
+        if held is None or held[0] is not self._master:
+            w = OrderedDict(self._encoder_master())
+            w.update(self._head_master())
+            assert list(w) == self.weight_names()
+            held = self._health_plan = (self._master, _health._Plan(list(w.values()),
+                                                                    what="weight_stats"))
+        return OrderedDict(zip(self.weight_shapes, held[1].run()))
 
     def count_params(self) -> int:
         return int(sum(int(np.prod(s)) for s in self.weight_shapes.values()))

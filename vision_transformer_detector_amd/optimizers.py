@@ -99,6 +99,40 @@ class Adam:
         st = self._state_for(model, scope)
         return st.m, st.v
 
+    # ---- numerical health of the optimizer's buffers (vtd_tensor_stats; health.py)
+    def _health(self, model, scope, which):
+        """The records of the state's gradient buffers ("g") or moments ("mv"): the uploaded
+        plan is kept on the state, which is rebuilt whenever its tensors are."""
+        from . import health as _health
+        st = self._state_for(model, scope)
+        plans = st.__dict__.setdefault("health_plans", {})
+        if which not in plans:
+            tensors = (list(st.grads.values()) if which == "g"
+                       else list(st.m.values()) + list(st.v.values()))
+            plans[which] = _health._Plan(tensors, what="Adam health")
+        return st, plans[which].run()
+
+    def gradient_stats(self, model, scope=None):
+        """health.TensorStat per gradient buffer, an OrderedDict keyed like `gradient_buffers`:
+        the gradients the last training call wrote (zeros before the first), NaN / Inf counts,
+        max / min, sum of squares and norm, from one launch pair and one host read."""
+        st, rec = self._health(model, scope, "g")
+        return OrderedDict(zip(st.grads, rec))
+
+    def moment_stats(self, model, scope=None):
+        """(m, v) as OrderedDicts of health.TensorStat keyed like `moments`: one launch pair
+        over both and one host read."""
+        st, rec = self._health(model, scope, "mv")
+        return (OrderedDict(zip(st.m, rec[:len(st.m)])), OrderedDict(zip(st.v, rec[len(st.m):])))
+
+    def global_norm(self, model, scope=None):
+        """sqrt(sum of squares over every gradient buffer), a float: what tf.linalg.global_norm
+        gives for the last step's gradients -- nan if any holds a NaN, else inf if any holds an
+        infinity.  Reporting only: the step does not clip by it (`clipnorm` and
+        `global_clipnorm` raise)."""
+        from . import health as _health
+        return _health.global_norm(self.gradient_stats(model, scope))
+
     def apply(self, model, stream=None, scope=None):
         """One step on `model` from the gradient buffers: a single vtd_train_step launch that
         updates the device masters, moments and packed operands of the scope's tensors (the
