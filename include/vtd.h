@@ -307,7 +307,13 @@ int vtd_fold_layernorm(const float* w32_dev, int N, int K, int ldw, const float*
  * finite result within the mode's tolerance (2e-5 of max(1, max |O|) for VTD_F32 /
  * VTD_BF16X3, 2e-2 for VTD_BF16), whatever the size or sign of the scores: no kernel's
  * running max costs a row more than fp32 rounding of its scores
- * (tests/test_gpu_attention_patterns.py). */
+ * (tests/test_gpu_attention_patterns.py).
+ * Size: rows are indexed with 64-bit products, so qkv and out may extend past 2^32 bytes
+ * (tests/test_gpu_big_operands.py).  One IMAGE is addressed through 32-bit offsets by the
+ * buffer-addressed bf16 kernels: the persistent kernel is chosen only while N * ldqkv * 2 and
+ * N * ldo * 2 are below 2^31 bytes (the streaming kernels run otherwise), and the long-sequence
+ * kernel of VTD_KNOB_ATTN_VARIANT 6 returns VTD_ERR_INVALID_ARG before any launch for such an
+ * image (tests/test_big_operands_host.py). */
 int vtd_attention(const void* qkv_dev, int B, int N, int heads, int dkp, int ldqkv,
                   float scale, void* out_dev, int ldo, int dtype, void* stream);
 
